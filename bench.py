@@ -29,6 +29,13 @@ planted communities holding 90 % of the edges, node ids RANDOMLY PERMUTED (what 
 one-off locality pass (CSRGraph.reorder, --reorder) relabels the nodes before training, as the METIS relabelling of BASELINE
 config 3 does; --reorder none measures the raw order, --no-permute the generator's community-sorted order.
 
+A plain run sets up, warms up, times the K steps and prints the line: `value` and `ms_per_step` (the wall time of one timed step)
+come from those K steps alone, and `roofline` / the launch tables from the HIP events inside them.  --full adds what takes
+runs of its own: the CPU baselines, the extra graphs, the other workloads (`other_workloads`), rmat27's aggregate-first step and,
+at N > 1, the per-rank diagnostics and the output all-gather.  --dump-outputs DIR writes what the last timed step computed
+(loss, a fixed seeded sample of at most 65 536 output rows, the updated parameters) as DIR/<name>.npy; the inputs are seeded, so
+two builds can be compared output for output.
+
 Rank 0 prints ONE JSON line; DESIGN.md section 7 explains every field.  `roofline.achieved` is the section-8(d) algorithmic rate
 (every edge charged one full feature row) of the dominant launch, timed live with HIP events on the launch stream.
 `roofline.frac` is a fraction (<= 1) of the 8 TB/s peak, defined in `roofline.frac_definition`: counter traffic of that very
@@ -85,13 +92,20 @@ def parse_args(argv=None):
                     help="multi-rank: RaCoM asynchronous gradient sharing (the bucket all-reduce of step t overlaps step t+1; "
                          "applied one step late, drained every sync period) instead of the synchronous form")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam instead of the one-launch flat Adam (dgll_amd/optim.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: CPU baselines, the extra graphs, the other workloads, rmat27's "
+                         "aggregate-first step, the multi-rank diagnostics and all-gather.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB: a fixed seeded sample of the rows of large outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra-graphs", "--no-worst-case", dest="no_extra", action="store_true",
-                    help="skip the extra SpMM measurements on the structure-free and raw-order graphs")
+                    help="--full: skip the extra SpMM measurements on the structure-free and raw-order graphs")
     ap.add_argument("--other-workloads", choices=["auto", "on", "off"], default="auto",
-                    help="append compact records of the other BASELINE configs (gat = config 4, minibatch = config 2, rmat27 = config 5 on "
-                         "one GPU) to the default line as `other_workloads`, each measured by a child `bench.py --workload X` run after the "
-                         "headline; auto = on for the default single-GPU products-sized sage run")
+                    help="--full: append compact records of the other BASELINE configs (gat = config 4, minibatch = config 2, rmat27 = "
+                         "config 5 on one GPU) to the default line as `other_workloads`, each measured by a child `bench.py --workload X "
+                         "--full` run after the headline; auto = on for the default single-GPU products-sized sage run")
     ap.add_argument("--full-line", action="store_true",
                     help="print the FULL record (definitions, launch tables, per-rank diagnostics, the complete child records) as the stdout "
                          "line, as rounds 1-5 did; default: a compact line of at most %d characters -- the full record goes to "
@@ -142,8 +156,16 @@ def parse_args(argv=None):
                     help="rmat27: the layer as A.(X.W) (the reference's order; N = 1 default) or as (A.X).W (N > 1: own rows only)")
     ap.add_argument("--rmat-no-rebalance", action="store_true",
                     help="rmat27, N > 1: keep the built-in cost ratio instead of re-fitting it on the live ranks and re-cutting once")
-    ap.add_argument("--rmat-no-allgather", action="store_true", help="rmat27, N > 1: skip the separately timed all-gather of the outputs")
-    return ap.parse_args(argv)
+    ap.add_argument("--rmat-no-allgather", action="store_true", help="rmat27, N > 1, --full: skip the separately timed all-gather of the outputs")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        if args.other_workloads == "on":
+            ap.error("--other-workloads on needs --full")
+        args.no_cpu_baseline = args.no_extra = args.rmat_no_allgather = True
+        args.other_workloads = "off"
+    return args
 
 
 def alg_bytes(nnz, n_rows, feat, x_bytes, y_bytes, weighted):
@@ -580,6 +602,43 @@ def barrier(c):
     torch.cuda.synchronize()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ROWS = 65536
+
+
+def dump_rows(t, rows=DUMP_ROWS):
+    """float32 host copy of a 2-D output: all of its rows, or (more than `rows` of them) a fixed seeded draw of `rows` rows kept
+    in ascending order -- the same rows in every run with the same arguments."""
+    n = t.shape[0]
+    if n > rows:
+        gen = torch.Generator()
+        gen.manual_seed(9001)
+        idx = torch.randperm(n, generator=gen)[:rows].sort().values.to(t.device)
+        t = t[idx]
+    return t.detach().float().cpu().numpy()
+
+
+def dump_outputs(path, loss=None, rows=None, model=None):
+    """--dump-outputs: DIR/<name>.npy for the last timed step -- `loss` (float64 [1]), every 2-D output in `rows` (name -> tensor,
+    sampled by dump_rows) and the model's parameters after the step's update (param.<name>, float32)."""
+    import numpy as np
+
+    arrays = {}
+    if loss is not None:
+        arrays["loss"] = np.array([float(loss)], dtype=np.float64)
+    for name, t in (rows or {}).items():
+        arrays[name] = dump_rows(t)
+    if model is not None:
+        for name, p in model.named_parameters():
+            arrays["param." + name] = p.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def timed_steps(args, c, step):
     """W untimed steps, then exactly K steps between barrier + synchronize; MAX over ranks.  Returns (elapsed s, last loss,
     launch summary, warm-up loss trace)."""
@@ -782,6 +841,7 @@ def run_sage(args, c):
     # (256 -> 47), so it aggregates the 47-wide product X.W_n instead of the 256-wide input (mean is linear).
     passes = 3 + 2
     world = c.world
+    last = {} if args.dump_outputs else None        # --dump-outputs: the latest step's model output (its storage, no autograd graph)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -798,6 +858,8 @@ def run_sage(args, c):
             if racom is not None:
                 racom.all_reduce_and_wait()
             opt.step()
+        if last is not None:
+            last["logits"] = out.detach()
         return loss
 
     if args.calibrate and c.world == 1:
@@ -813,6 +875,9 @@ def run_sage(args, c):
     per_rank = None
     if c.world > 1:
         torch.distributed.all_reduce(global_loss)
+    if args.dump_outputs and c.rank == 0:     # before anything below runs another step
+        dump_outputs(args.dump_outputs, global_loss, last, model)
+    if c.world > 1 and args.full:
         per_rank = per_rank_diagnostics(c, engine, step, racom=racom, opt_wrap=opt_wrap)
     if c.rank != 0:
         return None
@@ -851,6 +916,7 @@ def run_sage(args, c):
         result["warmup_loss_trace"] = trace
     if per_rank is not None:
         result["per_rank"] = per_rank
+    if engine is not None:
         result["config"]["exchange_form"] = engine.exchange.form
         result["config"]["halo_mode"] = halo_mode
     if c.world == 1 and not args.no_extra and not args.dataset:
@@ -936,6 +1002,7 @@ def run_gat(args, c):
         racom = ddist.RaCoM(params, c.dev, flat=None if args.torch_adam else opt)
     passes = 2 * 3                # per layer: forward, backward over the rows of A, backward over the rows of A^T
     world = c.world
+    last = {} if args.dump_outputs else None        # --dump-outputs: the latest step's model output (its storage, no autograd graph)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -953,6 +1020,8 @@ def run_gat(args, c):
         if racom is not None:
             racom.all_reduce_and_wait()
         opt.step()
+        if last is not None:
+            last["log_softmax" if args.gat_unfused_loss else "activations"] = (out if args.gat_unfused_loss else act).detach()
         return loss
 
     if args.calibrate and c.world == 1:
@@ -965,6 +1034,8 @@ def run_gat(args, c):
         torch.distributed.all_reduce(global_loss)
     if c.rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, global_loss, last, model)
     local_rows = n if engine is None else engine.part.n_own
     table, dense_table = launch_tables(timer.summary(), local_rows)
     roofline = None
@@ -1135,14 +1206,17 @@ def run_rmat27(args, c):
         with ops.LaunchTimer() as timer:
             t0 = time.perf_counter()
             for _ in range(steps):
-                fn()
+                out = fn()
             torch.cuda.synchronize()
             own = time.perf_counter() - t0
             barrier(c)
             elapsed = time.perf_counter() - t0
-        return own, elapsed, timer
+        return own, elapsed, timer, out
 
-    own_s, elapsed, timer = timed(step, args.steps)
+    own_s, elapsed, timer, out_last = timed(step, args.steps)
+    if args.dump_outputs and c.rank == 0:        # rank 0's rows of Y (its row block when N > 1)
+        dump_outputs(args.dump_outputs, rows={"y": out_last})
+    del out_last
     if c.world > 1:
         t = torch.tensor([elapsed], device=c.dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -1202,10 +1276,10 @@ def run_rmat27(args, c):
                    "slowest_rank": slow["rank"],
                    "imbalance_max_over_mean": slow["own_ms_per_step"] / (sum(r["own_ms_per_step"] for r in per_rank) / len(per_rank)),
                    "output_allgather": allgather})
-    if c.world == 1 and order == "transform-first":
+    if args.full and c.world == 1 and order == "transform-first":
         # the N > 1 ranks run the layer as (A.X).W: the same launch kinds in the other order, measured here so that a scaling
         # ratio can be formed between equal steps
-        _o, el2, _t = timed(step_aggregate_first, max(2, args.steps // 2))
+        _o, el2, _t, _y = timed(step_aggregate_first, max(2, args.steps // 2))
         result["aggregate_first_ms_per_step"] = el2 / max(2, args.steps // 2) * 1e3
     if not args.no_cpu_baseline and c.rank == 0 and c.world == 1:
         del x, y
@@ -1400,6 +1474,8 @@ def run_minibatch(args, c):
             loader_s, busy_s = pipe.load_seconds - l0, cpu_busy
             if prof is not None:
                 prof.disable()
+            if args.dump_outputs:                # the last timed batch's loss and the parameters after its update
+                dump_outputs(args.dump_outputs, loss.detach().double(), model=model)
             timer_cm.__enter__()
         t_body = time.perf_counter()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1635,7 +1711,7 @@ def compact_record(d):
 
 
 def run_other_workloads(args):
-    """The other BASELINE configs, each in a CHILD process (`bench.py --workload X`, started after this process has finished its own
+    """--full: the other BASELINE configs, each in a CHILD process (`bench.py --workload X --full`, started after this process has finished its own
     measurement and released its device memory), one after the other; a child that fails or overruns leaves an `error` record and
     never takes the headline with it."""
     torch.cuda.empty_cache()
@@ -1645,7 +1721,7 @@ def run_other_workloads(args):
         extra = overrides.get(name, tail if not overrides else None)      # tests name the records they want (small shapes)
         if extra is None:
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--seed", str(args.seed), "--full-line"] + list(extra)
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--seed", str(args.seed), "--full", "--full-line"] + list(extra)
         t0 = time.perf_counter()
         try:
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
@@ -1657,7 +1733,7 @@ def run_other_workloads(args):
         except subprocess.TimeoutExpired:
             out[name] = {"error": "no result within %d s" % limit}
         out[name]["wall_seconds"] = time.perf_counter() - t0
-        out[name]["command"] = "python bench.py --workload %s %s" % (workload, " ".join(extra))
+        out[name]["command"] = "python bench.py --workload %s --full %s" % (workload, " ".join(extra))
     return out
 
 

@@ -173,3 +173,44 @@ def test_compact_line_of_a_full_default_record_fits_the_drivers_reader(bench):
     # a failed child leaves a short error record
     bad = dict(full, other_workloads={"gat": {"error": "exit code 1", "stderr_tail": "x" * 600, "wall_seconds": 3.0, "command": "c"}})
     assert json.loads(bench.compact_line(bad, None))["other_workloads"]["gat"] == {"error": "exit code 1", "wall_seconds": 3.0}
+
+
+def test_a_plain_run_measures_the_headline_only_and_full_restores_the_rest(bench):
+    """Without --full: no CPU baseline, no extra graphs, no other workloads, no all-gather; --full gives back the defaults that
+    --no-cpu-baseline / --no-extra-graphs / --other-workloads still choose from; --steps is the number of timed steps."""
+    plain = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_extra and plain.rmat_no_allgather and plain.other_workloads == "off"
+    full = bench.parse_args(["--full"])
+    assert full.full and not full.no_cpu_baseline and not full.no_extra and not full.rmat_no_allgather and full.other_workloads == "auto"
+    assert bench.parse_args(["--full", "--no-cpu-baseline", "--other-workloads", "on"]).no_cpu_baseline
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--other-workloads", "on"])
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_float_arrays_with_a_fixed_row_sample(bench, tmp_path):
+    import numpy as np
+    import torch
+
+    torch.manual_seed(0)
+    out = torch.randn(bench.DUMP_ROWS + 1000, 9).to(torch.bfloat16)
+    small = torch.randn(10, 3)
+    model = torch.nn.Linear(5, 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), torch.tensor(2.5, dtype=torch.float64), {"logits": out, "small": small}, model)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["logits.npy", "loss.npy", "param.bias.npy", "param.weight.npy", "small.npy"]
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    logits = np.load(tmp_path / "a" / "logits.npy")
+    assert logits.shape == (bench.DUMP_ROWS, 9)                                         # a sample of the rows, all columns
+    rows = torch.randperm(out.shape[0], generator=torch.Generator().manual_seed(9001))[:bench.DUMP_ROWS].sort().values
+    assert np.array_equal(logits, out[rows].float().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())          # fewer rows than the sample: all of them
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "param.weight.npy"), model.weight.detach().numpy())
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), rows={"x": torch.zeros(bench.DUMP_ROWS, 300)})        # 78 MB: over the limit

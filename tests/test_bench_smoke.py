@@ -31,7 +31,8 @@ def _last_json(text):
 
 
 def test_bench_single_rank_contract():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line"] + SHAPE, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line"] + SHAPE, capture_output=True, text=True,
+                         timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -61,8 +62,8 @@ def test_bench_default_line_is_compact_and_parses(tmp_path):
     other = {"rmat27": ["--scale", "16", "--steps", "2", "--warmup", "1", "--cpu-sample-rows", "2000"]}
     full_path = str(tmp_path / "full.json")
     env = dict(os.environ, DGLL_BENCH_OTHER_ARGS=json.dumps(other), DGLL_BENCH_FULL_RECORD=full_path)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--other-workloads", "on"] + SHAPE, capture_output=True, text=True,
-                         timeout=900, env=env)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--other-workloads", "on"] + SHAPE, capture_output=True,
+                         text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     line = lines[-1]
@@ -166,7 +167,8 @@ def test_bench_gat_workload_one_and_two_ranks():
     the GAT cpu_baseline; two ranks (gloo, one GPU) reach the same loss through the partitioned edge-softmax."""
     shape = ["--workload", "gat", "--nodes", "20000", "--undirected-edges", "200000", "--hidden", "64", "--heads", "8", "--classes", "10",
              "--in-feats", "40", "--steps", "2", "--warmup", "1", "--cpu-sample-rows", "2000"]
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line"] + shape, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line"] + shape, capture_output=True, text=True,
+                         timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
     assert d["config"]["workload_id"] == "gat" and d["config"]["gather_passes_per_step"] == 6 and d["roofline"]["bound"] == "hbm"
@@ -225,11 +227,11 @@ def test_bench_rmat27_row_blocks_on_several_ranks(world):
     env = dict(os.environ, DGLL_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    one = _last_json(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--workload", "rmat27", "--scale", "16", "--steps", "2",
-                                     "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600).stdout)
+    one = _last_json(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line", "--workload", "rmat27", "--scale", "16",
+                                     "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600).stdout)
     assert one["config"]["layer_order"] == "transform-first" and one["aggregate_first_ms_per_step"] > 0 and len(one["per_rank"]) == 1
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--workload", "rmat27", "--scale", "16", "--steps", "2",
-                          "--warmup", "1", "--gpus", str(world)], capture_output=True, text=True, timeout=1200, env=env)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line", "--workload", "rmat27", "--scale", "16", "--steps",
+                          "2", "--warmup", "1", "--gpus", str(world)], capture_output=True, text=True, timeout=1200, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
     assert d["n_gpus"] == world and d["scaling"] == "strong" and d["config"]["layer_order"] == "aggregate-first"
@@ -270,8 +272,8 @@ def test_default_line_carries_the_other_baseline_configs():
         "rmat27": ["--scale", "16", "--steps", "2", "--warmup", "1", "--cpu-sample-rows", "2000"],
     }
     env = dict(os.environ, DGLL_BENCH_OTHER_ARGS=json.dumps(other))
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--other-workloads", "on", "--no-extra-graphs"] + SHAPE,
-                         capture_output=True, text=True, timeout=1500, env=env)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line", "--other-workloads", "on", "--no-extra-graphs"]
+                         + SHAPE, capture_output=True, text=True, timeout=1500, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
     ow = d["other_workloads"]
@@ -283,8 +285,8 @@ def test_default_line_carries_the_other_baseline_configs():
         assert set(("value", "unit", "cores", "kind", "sample")) <= set(rec["cpu_baseline"]) and rec["cpu_baseline"]["kind"] == "port"
     assert "gat_pass_over_spmm" not in ow["gat"] and ow["minibatch"]["batches_per_s"] > 0       # --no-extra-graphs: no SpMM comparison leg
     # the small-shape headline alone does not start them
-    assert "other_workloads" not in _last_json(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--no-extra-graphs"] + SHAPE,
-                                                              capture_output=True, text=True, timeout=600).stdout)
+    assert "other_workloads" not in _last_json(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line", "--no-extra-graphs"]
+                                                              + SHAPE, capture_output=True, text=True, timeout=600).stdout)
 
 
 def test_bench_runs_a_dataset_directory_in_the_ogb_raw_layout(tmp_path):
@@ -302,10 +304,41 @@ def test_bench_runs_a_dataset_directory_in_the_ogb_raw_layout(tmp_path):
     np.savetxt(raw / "edge.csv", np.stack([src[keep], dst[keep]], 1), fmt="%d", delimiter=",")
     np.savetxt(raw / "node-feat.csv", rng.standard_normal((n, f)).astype(np.float32), fmt="%.5f", delimiter=",")
     np.savetxt(raw / "node-label.csv", rng.integers(0, c, (n, 1)), fmt="%d", delimiter=",")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--dataset", str(tmp_path / "products"), "--hidden", "64",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--full-line", "--dataset", str(tmp_path / "products"), "--hidden", "64",
                           "--steps", "2", "--warmup", "1", "--cpu-sample-rows", "500", "--no-extra-graphs"],
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _last_json(res.stdout)
     assert d["data"].startswith("real: ") and d["config"]["nodes"] == n and d["loss"] == d["loss"]
     assert d["config"]["nnz"] > m and "other_workloads" not in d and d["cpu_baseline"]["value"] > 0      # symmetrised, duplicates merged
+
+
+def test_plain_run_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: exactly --steps timed steps and nothing measured besides them (no CPU baseline, no extra graphs, no other
+    workloads); --dump-outputs writes the last timed step's loss, its logits (all 20 000 rows here) and the updated parameters as
+    float .npy files -- and a second run with the same arguments gets the same inputs, hence the same outputs."""
+    import numpy as np
+
+    shape = list(SHAPE)
+    shape[shape.index("--steps") + 1] = "3"
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full-line", "--dump-outputs", str(out)] + shape,
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        d = _last_json(res.stdout)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "edges/s" and d["higher_is_better"] is True
+        assert len(d["per_step_gpu_ms"]) == 3 and abs(d["value"] - 5 * d["config"]["nnz"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        for key in ("cpu_baseline", "roofline_no_locality", "roofline_raw_order", "roofline_no_locality_raw_order", "other_workloads"):
+            assert key not in d, key
+        files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["loss"].tolist() == [d["loss"]] and files["logits"].shape == (20000, 10)
+        assert {k for k in files if k.startswith("param.")} == {"param.gcn%d.%s" % (i, w) for i in (1, 2, 3) for w in ("weight", "neighborAgg.weight")}
+        assert all(np.isfinite(a).all() for a in files.values())
+        dumps.append(files)
+    a, b = dumps
+    assert set(a) == set(b)
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=2e-2, atol=2e-2, err_msg=k)
