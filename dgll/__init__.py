@@ -24,6 +24,7 @@ _ALIASES = {
     "dgll.sampling": "dgll_amd.sampling",
     "dgll.sampling.base_sampler": "dgll_amd.sampling.base_sampler",
     "dgll.sampling.dgllsampler": "dgll_amd.sampling.dgllsampler",
+    "dgll.sampling.layerwise": "dgll_amd.sampling.layerwise",
     "dgll.dataloader": "dgll_amd.dataloader",
 }
 for _alias, _target in _ALIASES.items():

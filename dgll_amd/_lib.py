@@ -157,6 +157,16 @@ SIGNATURES = {
     "dgll_hip_gcn_fused_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dgll_hip_segment_max": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32]),
     "dgll_hip_segment_max_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _i32]),
+    "dgll_hip_lw_column_mass": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, C.c_uint32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "dgll_hip_lw_column_p": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "dgll_hip_lw_ctrl_words": (_i64, []),
+    "dgll_hip_lw_select": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i32, C.c_uint64, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "dgll_hip_lw_union_sorted": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "dgll_hip_lw_weights": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+    "dgll_hip_lw_block_count": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, C.c_uint32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dgll_hip_lw_block_fill": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, C.c_uint32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "dgll_host_philox4x32_10": (_i32, [_vp, _vp, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

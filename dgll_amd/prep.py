@@ -47,3 +47,19 @@ def to_torch_coo(graph):
     ind = torch.stack([graph.row_index(), graph.col.to(torch.int64)])
     val = graph.val if graph.val is not None else torch.ones(graph.nnz, dtype=torch.float32, device=graph.device)
     return torch.sparse_coo_tensor(ind, val, graph.shape)
+
+
+def sym_normalized_transpose(row, col, n, val=None, self_loops=True):
+    """normalize_lap(A + I) of the reference's FastGCN scripts (GPU Accelerator/utils.py:215-222): D^-1/2 (A + I)^T D^-1/2 with D
+    the ROW sums of A + I (+1e-20), as a CSRGraph with fp32 values.  Entry (i, j) of A + I lands at (j, i) scaled by
+    d_i^-1/2 d_j^-1/2: on directed input that is the transpose, not the symmetric normalisation of A.  Computed in fp64."""
+    row, col = row.to(torch.int64), col.to(torch.int64)
+    val = torch.ones(row.numel(), dtype=torch.float64, device=row.device) if val is None else val.to(torch.float64)
+    if self_loops:
+        eye = torch.arange(n, dtype=torch.int64, device=row.device)
+        row, col = torch.cat([row, eye]), torch.cat([col, eye])
+        val = torch.cat([val, torch.ones(n, dtype=torch.float64, device=row.device)])
+    rowsum = torch.zeros(n, dtype=torch.float64, device=row.device).index_add_(0, row, val) + 1e-20
+    d = rowsum.pow(-0.5)
+    d = torch.where(torch.isinf(d), torch.zeros_like(d), d)
+    return CSRGraph.from_coo(col, row, val * d[row] * d[col], (n, n))      # sorts and sums duplicates (A + I on a looped node)

@@ -561,6 +561,55 @@ int dgll_hip_softmax_xent_ex(void* stream, const void* logits, int64_t ldz, int 
 int dgll_hip_xent_reduce(void* stream, const float* row_loss, const int64_t* labels, int64_t n_rows, int n_classes, float* out4);
 
 
+/* ---- layer-wise importance sampling (LADIES / FastGCN; dgll_amd/sampling/layerwise.py) -------------------------------------
+ * L is a CSR (int64 rowptr, int32 col, fp32 val or NULL = 1) over n_total nodes; rows (int64) select its rows (NULL: all).
+ * info: int64[8] per layer, {candidates, s, columns of the block, nnz, error bits}; the host reads it once per layer.
+ * marker / mark: uint32[n_total] epoch tags (start zeroed, never cleared: every use passes a fresh non-zero epoch).
+ * Column mass: mass[c] = sum_{rows} rint(val^2 * 2^shift) (integer atomics, bitwise reproducible); cand (int32[n_total]) lists the
+ * distinct touched columns, their number in info[0]; totals = {sum of high halves, sum of low halves} of q (q = mass, or with
+ * flat sqrt(mass) in 2^-40 units).  Zeroes info[0..7] and totals first.  seg: int64[n_rows + 1] workspace (the rows' entry
+ * offsets: every pass over the entries is flat, whatever the row lengths; unused when rows is NULL).                         */
+int dgll_hip_lw_column_mass(void* stream, const int64_t* rowptr, const int32_t* col, const float* val, const int64_t* rows,
+                            int64_t n_rows, int64_t n_total, uint32_t* marker, uint32_t epoch, unsigned long long* mass,
+                            int shift, int flat, int32_t* cand, int64_t* info, unsigned long long* totals, int64_t* seg);
+/* p[i] = q(ids[i]) / sum q, for i < min(*count, cap) (count NULL: cap); fp64.                                                  */
+int dgll_hip_lw_column_p(void* stream, const int64_t* ids, const int64_t* count, int64_t cap, const unsigned long long* mass,
+                         int shift, int flat, const unsigned long long* totals, double* p);
+/* Words of the select's ctrl workspace (unsigned long long).                                                                   */
+int64_t dgll_hip_lw_ctrl_words(void);
+/* s = min(#{q > 0}, fanout) of the *cand_count candidates drawn without replacement with probability q / sum q, in draw order,
+ * into out_ids[0..s) (int64); s into info[1] and info[2].  Keys E / q, E = -log U, U from Philox4x32-10 with key = seed and
+ * counter = (node, 0, layer, const): a node's key depends on (seed, layer, node, q) only.  Workspaces: keys[cand_cap],
+ * ctrl[dgll_hip_lw_ctrl_words()], win_key / win_id [win_cap >= fanout].                                                        */
+int dgll_hip_lw_select(void* stream, const int32_t* cand, const int64_t* cand_count, int64_t cand_cap, const unsigned long long* mass,
+                       int shift, int flat, uint64_t seed, int layer, int64_t fanout, unsigned long long* keys, unsigned long long* ctrl,
+                       unsigned long long* win_key, int32_t* win_id, int64_t win_cap, int64_t* out_ids, int64_t* info);
+/* out = sorted unique(a[0..min(*a_count, a_cap)) u b[0..nb)), its length into info[2].  reps / out: a_cap + nb entries.         */
+int dgll_hip_lw_union_sorted(void* stream, const int64_t* a, const int64_t* a_count, int64_t a_cap, const int64_t* b, int64_t nb,
+                             int64_t n_total, uint32_t* marker, uint32_t epoch, int64_t* reps, unsigned long long* n_reps,
+                             int64_t* out, int64_t* info);
+/* Weights of m = min(*m_dev, cap) (m_dev NULL: cap) columns with probabilities p (draw order), fp64.  mode 0: the reference's
+ * estWRS_weights with n = n_total; mode 1: 1 / (p * s), s = *snum_dev (NULL: snum).  One workgroup.                            */
+int dgll_hip_lw_weights(void* stream, const double* p, const int64_t* m_dev, int64_t cap, const int64_t* snum_dev, int64_t snum,
+                        int64_t n_total, int mode, double* w);
+/* Block L[rows, cols] -- structure: maps cols (local id = position) through mark / local, counts the kept entries of every row
+ * and scans them into out_rowptr (int64[n_rows + 1]); nnz into info[3].  sorted: cols ascend (CSR order is local order), a
+ * wavefront per row.  Otherwise m_cap <= 4096 and the passes are flat over the entries: seg int64[n_rows + 1], bitmap uint32 and
+ * below int32 [n_rows * 128] workspaces, kept for dgll_hip_lw_block_fill.                                                    */
+int dgll_hip_lw_block_count(void* stream, const int64_t* rowptr, const int32_t* col, const int64_t* rows, int64_t n_rows,
+                            int64_t n_total, const int64_t* cols, const int64_t* m_dev, int64_t m_cap, uint32_t* mark,
+                            int32_t* local, uint32_t epoch, int sorted, int64_t* seg, uint32_t* bitmap, int32_t* below,
+                            int64_t* out_rowptr, int64_t* info);
+/* ... and values: out_col (int32 local ids, ascending within a row), out_val = val * w[local]; the same sorted flag and
+ * workspaces as the count.                                                                                                     */
+int dgll_hip_lw_block_fill(void* stream, const int64_t* rowptr, const int32_t* col, const float* val, const int64_t* rows,
+                           int64_t n_rows, int64_t n_total, const uint32_t* mark, const int32_t* local, uint32_t epoch,
+                           const double* w, int sorted, int64_t m, const int64_t* seg, const uint32_t* bitmap, const int32_t* below,
+                           const int64_t* out_rowptr, int32_t* out_col, float* out_val, int64_t* info);
+/* Philox4x32-10 of one counter (host; the samplers' generator, for tests).                                                     */
+int dgll_host_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
+
+
 /* ---- a10: H = relu(A_csr . (X[:, :actual_F] . W[:actual_F, :])) --------------------------------------------
  * launch_gcn_fused_kernel is the reference's own symbol with its exact signature
  * (/root/reference/dgll/FusedKernel/gcn_fused_kernel.cu:190-195, bound at gcn_extension.cpp:5-10,46-55): int32 CSR,
