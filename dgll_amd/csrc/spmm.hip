@@ -19,6 +19,13 @@
 //   * rows longer than the plan's threshold are cut into chunks that run as ordinary work items (scheduled
 //     FIRST, longest-processing-time style) and write fp32 partials that a tiny second kernel reduces in a
 //     fixed order -- no atomics anywhere, results are bit-reproducible;
+//   * which kernel runs the rows under the threshold (16-byte aligned operands; e = the plan's average edges per row):
+//       row-per-slot (spmm_rowslot_kernel)   rows of <= 16 lanes and e <= 24, rows of 32 lanes and e <= 4.5
+//       row-group (spmm_rowgroup_kernel)     bf16, no accumulate / gate: rows of 8 lanes and 24 < e <= 100, rows of 16 lanes and
+//                                            24 < e <= 64; two slots per row (4 resp. 2 rows per wavefront at a time)
+//       flattened (spmm_csr_flat_kernel)     fp32 rows of 16 / 32 lanes and e >= 8
+//       wave-per-row (spmm_csr_kernel)       everything else -- all rows of 32 and 64 lanes (F = 256), the accumulate / gate forms
+//     dgll_hip_debug_tune keys 5, 13 and 15 force or forbid the first three (15: 1 = never, 2 / 4 = slots per row);
 //   * optional XCD-contiguous row mapping (xcd_remap) for graphs whose neighbours are close in id space; off by
 //     default: on RMAT-like inputs (degree correlated with id) it unbalances the XCDs (measured -4 % .. -45 %).
 #include <algorithm>
@@ -585,6 +592,68 @@ __global__ __launch_bounds__(kBlock) void spmm_rowslot_kernel(const SpmmArgs a) 
     }
 }
 
+// ---- row-group variant: G = SLOTS / SPR output rows per wavefront at a time, SPR slots (SPR x LPR adjacent lanes) each ----------
+// Between the two kernels above (SPR = SLOTS: spmm_csr_kernel, SPR = 1: spmm_rowslot_kernel) for narrow rows of MEDIUM length -- the
+// 47-wide launches of the headline step: LPR = 8, 50 edges per row.  There the wave-per-row kernel pays per row 24 shuffles for 8
+// lanes' worth of result, a masked last round of 32 edge positions and a drained pipeline (row pointers -> index batch -> gathers ->
+// reduction -> epilogue -> a store from 8 lanes), while a slot of the row-per-slot kernel walks 50 edges four at a time.  Here, at
+// SPR = 2, four rows advance together on 16 lanes each: a round is 8 edges per row (at most 7 idle positions per row), the slots
+// of a row are combined by ONE level that stays inside a 16-lane DPP row, and row pointers, index batches, epilogue and store are
+// issued once for four rows.  The groups of a wavefront run until its longest row is done (gather_edges_grouped, gather.hpp);
+// the engine's row order keeps neighbouring rows of similar length.  Rows above the plan's threshold are skipped and run as chunks
+// exactly as above.  The accumulate / gate forms (EXTRA) stay on the kernels above: this one is kept within 64 VGPRs.
+template <typename XT, typename YT, int EPV, int LPR, int SPR, bool HAS_VAL>
+__global__ __launch_bounds__(kBlock) void spmm_rowgroup_kernel(const SpmmArgs a) {
+    constexpr int SLOTS = kWave / LPR, G = SLOTS / SPR, GL = kWave / G, U = 4;
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int sub = lane % LPR, grp = lane / GL;
+    const int c0 = ((int)blockIdx.y * LPR + sub) * EPV;
+    const bool col_ok = c0 < a.feat;
+    const XT* xcol = static_cast<const XT*>(a.X) + (col_ok ? c0 : 0);
+    uint32_t bid = blockIdx.x;
+
+    if (bid < a.chunk_blocks) {  // ---- a chunk of a long row: identical to spmm_csr_kernel's chunk items
+        const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
+        if (chunk >= a.n_chunks) return;
+        float acc[EPV];
+#pragma unroll
+        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
+        gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]),
+                                               uniform64(a.chunk_end[chunk]), lane, acc);
+        if (lane < LPR && col_ok) {
+            float* w = a.ws + chunk * a.ws_ld + c0;
+#pragma unroll
+            for (int i = 0; i < EPV; ++i) w[i] = acc[i];
+        }
+        return;
+    }
+    bid -= a.chunk_blocks;
+    const uint32_t ld32 = (uint32_t)a.ldx;
+    const bool writer = col_ok && lane % GL < LPR;                                      // the first slot of every lane group
+    const bool full = c0 + EPV <= a.feat;
+    const int64_t row0 = ((int64_t)bid * kWavesPerBlock + wave) * a.rows_per_wave;     // rows_per_wave is a multiple of G
+    for (int r = 0; r < a.rows_per_wave; r += G) {
+        if (row0 + r >= a.n_rows) return;
+        const int64_t row = row0 + r + grp;
+        int64_t b = 0, e = 0;
+        if (row < a.n_rows) { b = a.rowptr[row]; e = a.rowptr[row + 1]; }
+        const int64_t full_len = e - b;
+        const bool mine = row < a.n_rows && !(a.threshold > 0 && full_len > a.threshold);   // long rows: handled as chunks
+        const int n = mine ? (int)full_len : 0;
+        float acc[EPV];
+#pragma unroll
+        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
+        gather_edges_grouped<XT, EPV, LPR, SPR, HAS_VAL, U>(a.col, a.val, xcol, ld32, b, n, lane, acc);
+        if (!mine || !writer) continue;
+        YT* yrow = static_cast<YT*>(a.Y) + row * a.ldy;
+        RowVec<YT, EPV> prev, gatev;
+        const float scale = a.row_scale ? a.row_scale[row]
+                                        : ((a.reduce == DGLL_REDUCE_MEAN && n > 0) ? 1.0f / (float)n : 1.0f);
+        finish_row<YT, EPV, false>(yrow, c0, a.feat, scale, a.epilogue, a.bias, acc, 0, nullptr, full, prev, gatev);
+    }
+}
+
 // Second pass for long rows: sum the chunk partials in chunk order, then the same epilogue.  One wavefront per long row,
 // four columns per lane (float4 reads of the partials); most long rows have only two or three chunks.
 template <typename YT>
@@ -635,6 +704,15 @@ __global__ __launch_bounds__(kBlock) void spmm_long_finalize_kernel(const SpmmAr
 }
 
 static int ws_ld_for(int feat) { return (feat + 7) & ~7; }
+// upper edges of the row-group kernel's band (edges per row, plan average), rows of 8 and of 16 lanes; lower edge: the row-per-slot
+// kernel's 24.  Measured on MI355X (tools/rowgroup_ab.py --band: the products-sized bench graph, thinned and doubled), bf16,
+// unweighted / weighted, against the wave-per-row kernel; two slots per row beat four everywhere (idle share of the lane groups
+// on the bench graph 11 % against 23 %, the wave-per-row kernel's last rounds 40 %):
+//   edges per row      25          38          51          76          101
+//   F = 47         -40 / -34 % -32 / -26 % -28 / -22 % -16 /  -9 % -13 /  -7 %
+//   F = 64         -42 / -34 % -32 / -25 % -29 / -21 % -15 /  -9 % -12 /  -6 %
+//   F = 100        -12 /  -9 %  -8 /  -6 %  -6 /  -6 %  -2 /  -2 %  -3 /  -2 %    (two rows per wavefront: little left to share)
+constexpr double kRowGroupMaxAvgLen8 = 100.0, kRowGroupMaxAvgLen16 = 64.0;
 
 // Tuning knobs (diagnostics; defaults are the shipped configuration).  Set through dgll_hip_debug_tune().
 static int g_tune_unroll = 4;        // gathers in flight per lane (2, 4 or 8; 8 only for the widest variants)
@@ -644,6 +722,8 @@ static int g_tune_threshold = 0;     // 0 = plan default (256)
 static int g_tune_rowslot = 0;       // 0 = automatic choice of the row-per-slot kernel, 1 = never, 2 = whenever it applies
 static int g_tune_flat = 0;          // flattened kernel (spmm_csr_flat_kernel): 0 = automatic, 1 = never, 2 = whenever the plan has its schedule
 static int g_tune_flat_edges = 256;  // edges per wave of the flattened schedule (read when a plan is created)
+static int g_tune_rowgroup = 0;      // row-group kernel (spmm_rowgroup_kernel): 0 = automatic, 1 = never (the choice before it existed),
+                                     // 2 / 4 = wherever it is instantiated, with that many slots per row
 
 template <typename XT, typename YT, int EPV, int LPR, int U>
 static hipError_t launch_u(const SpmmArgs& a, dim3 grid, hipStream_t s) {
@@ -700,6 +780,21 @@ static hipError_t launch_rowslot_lpr(const SpmmArgs& a, int lpr, dim3 grid, hipS
         case 16: return launch_rowslot<XT, YT, EPV, 16>(a, grid, s);
         default: return launch_rowslot<XT, YT, EPV, 32>(a, grid, s);
     }
+}
+
+template <typename XT, typename YT, int EPV, int LPR, int SPR>
+static hipError_t launch_rowgroup(const SpmmArgs& a, dim3 grid, hipStream_t s) {
+    if (a.val) hipLaunchKernelGGL((spmm_rowgroup_kernel<XT, YT, EPV, LPR, SPR, true>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((spmm_rowgroup_kernel<XT, YT, EPV, LPR, SPR, false>), grid, dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+// instantiated for bf16 rows of 8 lanes (2 or 4 slots per row) and of 16 lanes (2 slots per row)
+template <typename YT>
+static hipError_t launch_rowgroup_lpr(const SpmmArgs& a, int lpr, int spr, dim3 grid, hipStream_t s) {
+    if (lpr == 16) return launch_rowgroup<bf16_t, YT, 8, 16, 2>(a, grid, s);
+    if (spr == 4) return launch_rowgroup<bf16_t, YT, 8, 8, 4>(a, grid, s);
+    return launch_rowgroup<bf16_t, YT, 8, 8, 2>(a, grid, s);
 }
 
 template <typename XT, typename YT, int EPV, int LPR>
@@ -847,6 +942,7 @@ DGLL_API int dgll_hip_debug_tune(int key, int value) {
         case 5: g_tune_rowslot = value; break;
         case 13: g_tune_flat = value; break;
         case 14: g_tune_flat_edges = value; break;
+        case 15: g_tune_rowgroup = value; break;
         case 7: break;                              // (retired: unroll depth of the first-generation GAT backward passes)
         case 9: g_tune_gat_gen = value; break;
         case 11: g_tune_res_per_cu = value; break;
@@ -996,7 +1092,36 @@ int dgll_spmm_csr_impl(void* stream, const dgll_csr_plan* plan, const int64_t* r
             if (g_tune_rows_per_wave > 0) a.rows_per_wave = (g_tune_rows_per_wave + slots - 1) / slots * slots;
         }
     }
-    if (rowslot) {   // the grid depends on rows_per_wave: recompute
+    // row-group kernel: bf16 rows of 8 lanes (F = 33 .. 64) and of 16 lanes (F = 65 .. 128) ABOVE the row-per-slot band, two slots
+    // per row (band edges and measurements: kRowGroupMaxAvgLen8 / 16 above); plain aggregation only
+    // (the accumulate / gate forms stay on the wave-per-row kernel).  dgll_hip_debug_tune(15, 1) gives the choice before this kernel
+    // existed, (15, 2) / (15, 4) force it wherever it is instantiated (16-lane rows included) with that many slots per row.
+    int rowgroup_spr = 0;
+    if (fast && !rowslot && !only_long && x_dtype == DGLL_BF16 && !accumulate && !gate && g_tune_rowgroup != 1 &&
+        g_tune_unroll == 4 && !(a.flags & 1)) {
+        const int vecs = (feat + epv - 1) / epv;
+        const double avg_len = plan ? (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) : 1e9;
+        if (g_tune_rowgroup == 2 || g_tune_rowgroup == 4) {
+            if (vecs > 4 && vecs <= 8) rowgroup_spr = g_tune_rowgroup;
+            else if (vecs > 8 && vecs <= 16) rowgroup_spr = 2;
+        } else if (avg_len > 24.0 && ((vecs > 4 && vecs <= 8 && avg_len <= kRowGroupMaxAvgLen8) ||
+                                      (vecs > 8 && vecs <= 16 && avg_len <= kRowGroupMaxAvgLen16))) {
+            rowgroup_spr = 2;
+        }
+    }
+    if (rowgroup_spr) {
+        const int vecs = (feat + epv - 1) / epv;
+        const int lpr = vecs <= 8 ? 8 : 16;
+        const int rows = kWave / lpr / rowgroup_spr;           // rows per wavefront at a time
+        a.rows_per_wave = (std::max(a.rows_per_wave, 1) + rows - 1) / rows * rows;
+        const int64_t waves2 = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
+        const int64_t row_blocks2 = (waves2 + kWavesPerBlock - 1) / kWavesPerBlock;
+        DGLL_REQUIRE(row_blocks2 + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
+        a.row_blocks = (uint32_t)row_blocks2;
+        dim3 grid((uint32_t)(row_blocks2 + chunk_blocks), 1u);
+        if (y_dtype == DGLL_BF16) err = launch_rowgroup_lpr<bf16_t>(a, lpr, rowgroup_spr, grid, s);
+        else err = launch_rowgroup_lpr<float>(a, lpr, rowgroup_spr, grid, s);
+    } else if (rowslot) {   // the grid depends on rows_per_wave: recompute
         const int64_t waves2 = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
         const int64_t row_blocks2 = (waves2 + kWavesPerBlock - 1) / kWavesPerBlock;
         DGLL_REQUIRE(row_blocks2 + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
