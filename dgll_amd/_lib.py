@@ -40,6 +40,12 @@ class BatchLoad(C.Structure):
                 ("upload_blocks", C.c_int)]
 
 
+class SpmmChoice(C.Structure):
+    """include/dgll_hip.h: struct dgll_spmm_choice (dgll_hip_debug_spmm_choice)."""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "epv", "lpr", "spr", "unroll", "prefetch", "rows_per_wave", "grid_y")] + \
+               [("row_blocks", C.c_int64), ("chunk_blocks", C.c_int64)]
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -66,6 +72,7 @@ SIGNATURES = {
     "dgll_hip_last_error": (C.c_char_p, []),
     "dgll_hip_device_info": (_i32, [_i32, C.c_char_p, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
     "dgll_hip_debug_tune": (_i32, [_i32, _i32]),
+    "dgll_hip_debug_spmm_choice": (_i32, [_i32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dgll_hip_csr_plan_create": (_i32, [_vp, _vp, _i64, _i64, _i32, C.POINTER(_vp)]),
     "dgll_hip_csr_plan_destroy": (None, [_vp]),
     "dgll_hip_csr_plan_workspace_bytes": (_sz, [_vp, _i32]),

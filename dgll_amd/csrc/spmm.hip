@@ -19,13 +19,9 @@
 //   * rows longer than the plan's threshold are cut into chunks that run as ordinary work items (scheduled
 //     FIRST, longest-processing-time style) and write fp32 partials that a tiny second kernel reduces in a
 //     fixed order -- no atomics anywhere, results are bit-reproducible;
-//   * which kernel runs the rows under the threshold (16-byte aligned operands; e = the plan's average edges per row):
-//       row-per-slot (spmm_rowslot_kernel)   rows of <= 16 lanes and e <= 24, rows of 32 lanes and e <= 4.5
-//       row-group (spmm_rowgroup_kernel)     bf16, no accumulate / gate: rows of 8 lanes and 24 < e <= 100, rows of 16 lanes and
-//                                            24 < e <= 64; two slots per row (4 resp. 2 rows per wavefront at a time)
-//       flattened (spmm_csr_flat_kernel)     fp32 rows of 16 / 32 lanes and e >= 8
-//       wave-per-row (spmm_csr_kernel)       everything else -- all rows of 32 and 64 lanes (F = 256), the accumulate / gate forms
-//     dgll_hip_debug_tune keys 5, 13 and 15 force or forbid the first three (15: 1 = never, 2 / 4 = slots per row);
+//   * four kernels run the rows under the threshold -- wave-per-row (spmm_csr_kernel), flattened (spmm_csr_flat_kernel), row-per-slot
+//     (spmm_rowslot_kernel), row-group (spmm_rowgroup_kernel); which one a launch gets is decided by spmm_choose() below, the rule
+//     and its measurements are written there and nowhere else (dgll_hip_debug_spmm_choice() shows it without a device);
 //   * optional XCD-contiguous row mapping (xcd_remap) for graphs whose neighbours are close in id space; off by
 //     default: on RMAT-like inputs (degree correlated with id) it unbalances the XCDs (measured -4 % .. -45 %).
 #include <algorithm>
@@ -87,7 +83,7 @@ struct SpmmArgs {
     int ws_ld;
     uint32_t chunk_blocks, row_blocks;
     int rows_per_wave;
-    int flags;  // bit 0: XCD-contiguous row mapping
+    int flags;  // kSpmm* bits below
     const float* row_scale;   // optional fp32[n_rows]: replaces the reduce's own scale (split adjacencies share one degree)
     int accumulate;           // 1: Y = epi(scale * (A.X + Y));  2: Y += gate(scale * A.X), rows without edges untouched
     const void* gate;         // optional [n_rows, ldg] of Y's type: outputs are zeroed where gate <= 0 (fused ReLU backward)
@@ -95,6 +91,11 @@ struct SpmmArgs {
     const int64_t* flat_row0; // flattened kernel: first row of every wave's share (plan->d_flat_row0), n_flat + 1 entries
     int64_t n_flat;
 };
+
+// SpmmArgs::flags (bits 0 and 2 are dgll_hip_debug_tune(2, v)'s; bit 1 is set by the host when it applies)
+constexpr int kSpmmXcdRemap = 1;      // XCD-contiguous row mapping (spmm_csr_kernel)
+constexpr int kSpmmAligned16 = 2;     // operands and leading dimensions are 16-byte aligned
+constexpr int kSpmmPrefetchNext = 4;  // next-row index prefetch (the PF instantiations of spmm_csr_kernel)
 
 template <typename T> __device__ __forceinline__ float load_one(const T* p);
 template <> __device__ __forceinline__ float load_one<float>(const float* p) { return *p; }
@@ -203,6 +204,48 @@ __device__ __forceinline__ void finish_row(YT* __restrict__ y, int c0, int feat,
     }
 }
 
+// scale of a finished row of `len` edges: the caller's row_scale, else the reduce's own
+template <typename L> __device__ __forceinline__ float spmm_row_scale(const SpmmArgs& a, int64_t row, L len) {
+    return a.row_scale ? a.row_scale[row] : ((a.reduce == DGLL_REDUCE_MEAN && len > 0) ? 1.0f / (float)len : 1.0f);
+}
+
+// Row `row` of `len` edges is complete in acc (this lane's EPV columns from c0, which lie in the row): the packed prev / gatev
+// loads of the EXTRA forms, the scale, finish_row.  Called AFTER the gather (see finish_row's comment on the register budget).
+template <typename YT, int EPV, bool EXTRA, typename L>
+__device__ __forceinline__ void spmm_finish_row(const SpmmArgs& a, int64_t row, L len, int c0, float (&acc)[EPV]) {
+    YT* yrow = static_cast<YT*>(a.Y) + row * a.ldy;
+    const bool full = c0 + EPV <= a.feat;
+    RowVec<YT, EPV> prev, gatev;
+    const YT* grow = nullptr;
+    if constexpr (EXTRA) {
+        grow = a.gate ? static_cast<const YT*>(a.gate) + row * a.ldg : nullptr;
+        if (full) {
+            if (a.accumulate) prev.load(yrow + c0);
+            if (grow) gatev.load(grow + c0);
+        }
+    }
+    finish_row<YT, EPV, EXTRA>(yrow, c0, a.feat, spmm_row_scale(a, row, len), a.epilogue, a.bias, acc, a.accumulate, grow, full, prev,
+                               gatev);
+}
+
+// A chunk of a long row (the work items every row kernel runs FIRST, blocks [0, chunk_blocks)): fp32 partial into the workspace.
+template <typename XT, int EPV, int LPR, bool HAS_VAL, int U>
+__device__ __forceinline__ void spmm_chunk_item(const SpmmArgs& a, const XT* __restrict__ xcol, int c0, bool col_ok, int lane, int wave,
+                                                uint32_t bid) {
+    const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
+    if (chunk >= a.n_chunks) return;
+    float acc[EPV];
+#pragma unroll
+    for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
+    gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]), uniform64(a.chunk_end[chunk]),
+                                           lane, acc);
+    if (lane < LPR && col_ok) {
+        float* w = a.ws + chunk * a.ws_ld + c0;
+#pragma unroll
+        for (int i = 0; i < EPV; ++i) w[i] = acc[i];
+    }
+}
+
 template <typename XT, typename YT, int EPV, int LPR, bool HAS_VAL, int U, bool EXTRA, bool PF = false>
 __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const SpmmArgs a) {
     const int lane = lane_id();
@@ -213,26 +256,12 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const SpmmArgs a) {
     const XT* xcol = static_cast<const XT*>(a.X) + (col_ok ? c0 : 0);  // idle lanes re-read column 0, never store
     uint32_t bid = blockIdx.x;
 
-    if (bid < a.chunk_blocks) {  // ---- a chunk of a long row: fp32 partial into the workspace
-        const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
-        if (chunk >= a.n_chunks) return;
-        float acc[EPV];
-#pragma unroll
-        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
-        gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]),
-                                               uniform64(a.chunk_end[chunk]), lane, acc);
-        if (lane < LPR && col_ok) {
-            float* w = a.ws + chunk * a.ws_ld + c0;
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) w[i] = acc[i];
-        }
-        return;
-    }
+    if (bid < a.chunk_blocks) { spmm_chunk_item<XT, EPV, LPR, HAS_VAL, U>(a, xcol, c0, col_ok, lane, wave, bid); return; }
 
     bid -= a.chunk_blocks;
-    if (a.flags & 1) bid = xcd_remap(bid, a.row_blocks);
+    if (a.flags & kSpmmXcdRemap) bid = xcd_remap(bid, a.row_blocks);
     const int64_t row0 = ((int64_t)bid * kWavesPerBlock + wave) * a.rows_per_wave;
-    // flags bit 2: the NEXT row's first index batch is requested before this row's gathers (one dependent load less per row)
+    // kSpmmPrefetchNext: the NEXT row's first index batch is requested before this row's gathers (one dependent load less per row)
     constexpr bool pf = PF;        // (a template parameter: the two extra live registers cost the default variant a wavefront per SIMD)
     int64_t nb_ = 0, ne_ = 0;
     int ncol = 0;
@@ -270,26 +299,8 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const SpmmArgs a) {
         float acc[EPV];
 #pragma unroll
         for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
-        YT* yrow = static_cast<YT*>(a.Y) + row * a.ldy;
-        const bool writer = lane < LPR && col_ok;
-        const bool full = c0 + EPV <= a.feat;
-        RowVec<YT, EPV> prev, gatev;
-        const YT* grow = nullptr;
-        if constexpr (EXTRA) {
-            grow = a.gate ? static_cast<const YT*>(a.gate) + row * a.ldg : nullptr;
-        }
         gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, b, e, lane, acc, pf, fcol, fval);
-        if constexpr (EXTRA) {
-            if (writer && full) {
-                if (a.accumulate) prev.load(yrow + c0);
-                if (grow) gatev.load(grow + c0);
-            }
-        }
-        if (writer) {
-            const float scale = a.row_scale ? a.row_scale[row]
-                                            : ((a.reduce == DGLL_REDUCE_MEAN && e > b) ? 1.0f / (float)(e - b) : 1.0f);
-            finish_row<YT, EPV, EXTRA>(yrow, c0, a.feat, scale, a.epilogue, a.bias, acc, a.accumulate, grow, full, prev, gatev);
-        }
+        if (lane < LPR && col_ok) spmm_finish_row<YT, EPV, EXTRA>(a, row, e - b, c0, acc);
     }
 }
 
@@ -318,21 +329,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_flat_kernel(const SpmmArgs a)
     const XT* xcol = static_cast<const XT*>(a.X) + (col_ok ? c0 : 0);
     uint32_t bid = blockIdx.x;
 
-    if (bid < a.chunk_blocks) {  // ---- a chunk of a long row: identical to spmm_csr_kernel's chunk items
-        const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
-        if (chunk >= a.n_chunks) return;
-        float acc[EPV];
-#pragma unroll
-        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
-        gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]),
-                                               uniform64(a.chunk_end[chunk]), lane, acc);
-        if (lane < LPR && col_ok) {
-            float* w = a.ws + chunk * a.ws_ld + c0;
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) w[i] = acc[i];
-        }
-        return;
-    }
+    if (bid < a.chunk_blocks) { spmm_chunk_item<XT, EPV, LPR, HAS_VAL, U>(a, xcol, c0, col_ok, lane, wave, bid); return; }
     bid -= a.chunk_blocks;
     const int64_t w = (int64_t)bid * kWavesPerBlock + wave;
     if (w >= a.n_flat) return;
@@ -343,7 +340,6 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_flat_kernel(const SpmmArgs a)
     const int64_t p_end = uniform64(a.rowptr[r_end]);
     int64_t p = rb;                       // next edge to consume; invariant: acc = sum over the current row's edges [rb, p)
     const bool writer = lane < LPR && col_ok;
-    const bool full = c0 + EPV <= a.feat;
     const uint32_t ld32 = (uint32_t)a.ldx;
     const int thr = a.threshold;
     float acc[EPV];
@@ -362,21 +358,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_flat_kernel(const SpmmArgs a)
         if constexpr (EXTRA) {
             if (a.accumulate == 2 && re == rb) emit = false;       // increment form: nothing to add to a row without edges
         }
-        if (emit) {
-            YT* yrow = static_cast<YT*>(a.Y) + r * a.ldy;
-            RowVec<YT, EPV> prev, gatev;
-            const YT* grow = nullptr;
-            if constexpr (EXTRA) {
-                grow = a.gate ? static_cast<const YT*>(a.gate) + r * a.ldg : nullptr;
-                if (full) {
-                    if (a.accumulate) prev.load(yrow + c0);
-                    if (grow) gatev.load(grow + c0);
-                }
-            }
-            const float scale = a.row_scale ? a.row_scale[r]
-                                            : ((a.reduce == DGLL_REDUCE_MEAN && re > rb) ? 1.0f / (float)(re - rb) : 1.0f);
-            finish_row<YT, EPV, EXTRA>(yrow, c0, a.feat, scale, a.epilogue, a.bias, acc, a.accumulate, grow, full, prev, gatev);
-        }
+        if (emit) spmm_finish_row<YT, EPV, EXTRA>(a, r, re - rb, c0, acc);
 #pragma unroll
         for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
         ++r;
@@ -512,21 +494,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowslot_kernel(const SpmmArgs a) 
     const XT* xcol = static_cast<const XT*>(a.X) + (col_ok ? c0 : 0);
     uint32_t bid = blockIdx.x;
 
-    if (bid < a.chunk_blocks) {  // ---- a chunk of a long row: identical to spmm_csr_kernel's chunk items
-        const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
-        if (chunk >= a.n_chunks) return;
-        float acc[EPV];
-#pragma unroll
-        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
-        gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]),
-                                               uniform64(a.chunk_end[chunk]), lane, acc);
-        if (lane < LPR && col_ok) {
-            float* w = a.ws + chunk * a.ws_ld + c0;
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) w[i] = acc[i];
-        }
-        return;
-    }
+    if (bid < a.chunk_blocks) { spmm_chunk_item<XT, EPV, LPR, HAS_VAL, U>(a, xcol, c0, col_ok, lane, wave, bid); return; }
     bid -= a.chunk_blocks;
     const uint32_t ld32 = (uint32_t)a.ldx;
     const int64_t row0 = ((int64_t)bid * kWavesPerBlock + wave) * a.rows_per_wave;     // rows_per_wave is a multiple of SLOTS
@@ -574,21 +542,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowslot_kernel(const SpmmArgs a) 
                 for (int i = 0; i < EPV; ++i) acc[i] = HAS_VAL ? fmaf(w[u], f[i], acc[i]) : acc[i] + f[i];
             }
         }
-        if (!mine || !col_ok) continue;
-        YT* yrow = static_cast<YT*>(a.Y) + row * a.ldy;
-        const bool full = c0 + EPV <= a.feat;
-        RowVec<YT, EPV> prev, gatev;
-        const YT* grow = nullptr;
-        if constexpr (EXTRA) {
-            grow = a.gate ? static_cast<const YT*>(a.gate) + row * a.ldg : nullptr;
-            if (full) {
-                if (a.accumulate) prev.load(yrow + c0);
-                if (grow) gatev.load(grow + c0);
-            }
-        }
-        const float scale = a.row_scale ? a.row_scale[row]
-                                        : ((a.reduce == DGLL_REDUCE_MEAN && n > 0) ? 1.0f / (float)n : 1.0f);
-        finish_row<YT, EPV, EXTRA>(yrow, c0, a.feat, scale, a.epilogue, a.bias, acc, a.accumulate, grow, full, prev, gatev);
+        if (mine && col_ok) spmm_finish_row<YT, EPV, EXTRA>(a, row, n, c0, acc);
     }
 }
 
@@ -613,25 +567,10 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup_kernel(const SpmmArgs a)
     const XT* xcol = static_cast<const XT*>(a.X) + (col_ok ? c0 : 0);
     uint32_t bid = blockIdx.x;
 
-    if (bid < a.chunk_blocks) {  // ---- a chunk of a long row: identical to spmm_csr_kernel's chunk items
-        const int64_t chunk = __builtin_amdgcn_readfirstlane((int)(bid * kWavesPerBlock + wave));
-        if (chunk >= a.n_chunks) return;
-        float acc[EPV];
-#pragma unroll
-        for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
-        gather_edges<XT, EPV, LPR, HAS_VAL, U>(a.col, a.val, xcol, a.ldx, uniform64(a.chunk_begin[chunk]),
-                                               uniform64(a.chunk_end[chunk]), lane, acc);
-        if (lane < LPR && col_ok) {
-            float* w = a.ws + chunk * a.ws_ld + c0;
-#pragma unroll
-            for (int i = 0; i < EPV; ++i) w[i] = acc[i];
-        }
-        return;
-    }
+    if (bid < a.chunk_blocks) { spmm_chunk_item<XT, EPV, LPR, HAS_VAL, U>(a, xcol, c0, col_ok, lane, wave, bid); return; }
     bid -= a.chunk_blocks;
     const uint32_t ld32 = (uint32_t)a.ldx;
     const bool writer = col_ok && lane % GL < LPR;                                      // the first slot of every lane group
-    const bool full = c0 + EPV <= a.feat;
     const int64_t row0 = ((int64_t)bid * kWavesPerBlock + wave) * a.rows_per_wave;     // rows_per_wave is a multiple of G
     for (int r = 0; r < a.rows_per_wave; r += G) {
         if (row0 + r >= a.n_rows) return;
@@ -645,12 +584,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup_kernel(const SpmmArgs a)
 #pragma unroll
         for (int i = 0; i < EPV; ++i) acc[i] = 0.0f;
         gather_edges_grouped<XT, EPV, LPR, SPR, HAS_VAL, U>(a.col, a.val, xcol, ld32, b, n, lane, acc);
-        if (!mine || !writer) continue;
-        YT* yrow = static_cast<YT*>(a.Y) + row * a.ldy;
-        RowVec<YT, EPV> prev, gatev;
-        const float scale = a.row_scale ? a.row_scale[row]
-                                        : ((a.reduce == DGLL_REDUCE_MEAN && n > 0) ? 1.0f / (float)n : 1.0f);
-        finish_row<YT, EPV, false>(yrow, c0, a.feat, scale, a.epilogue, a.bias, acc, 0, nullptr, full, prev, gatev);
+        if (mine && writer) spmm_finish_row<YT, EPV, false>(a, row, n, c0, acc);
     }
 }
 
@@ -664,9 +598,7 @@ __global__ __launch_bounds__(kBlock) void spmm_long_finalize_kernel(const SpmmAr
     if (li >= n_long) return;
     const int64_t row = long_row[li];
     const int cb = long_chunk0[li], ce = long_chunk0[li + 1];
-    float scale = 1.0f;
-    if (a.row_scale) scale = a.row_scale[row];
-    else if (a.reduce == DGLL_REDUCE_MEAN) scale = 1.0f / (float)(a.rowptr[row + 1] - a.rowptr[row]);
+    const float scale = spmm_row_scale(a, row, a.rowptr[row + 1] - a.rowptr[row]);
     YT* y = static_cast<YT*>(a.Y) + row * a.ldy;
     const YT* gate = a.gate ? static_cast<const YT*>(a.gate) + row * a.ldg : nullptr;
     for (int f = lane * 4; f < a.feat; f += kWave * 4) {   // ws_ld is a multiple of 8 floats: the float4 stays in the row
@@ -697,13 +629,43 @@ __global__ __launch_bounds__(kBlock) void spmm_long_finalize_kernel(const SpmmAr
             if (a.accumulate == 2) t += load_one<YT>(y + f + i);
             v[i] = t;
         }
-        if (f + 4 <= a.feat && (a.flags & 2)) VecIO<YT, 4>::store(y + f, v);     // flags bit 1: rows are 16-byte aligned
+        if (f + 4 <= a.feat && (a.flags & kSpmmAligned16)) VecIO<YT, 4>::store(y + f, v);
         else
             for (int i = 0; i < 4; ++i) if (f + i < a.feat) store_one<YT>(y + f + i, v[i]);
     }
 }
 
 static int ws_ld_for(int feat) { return (feat + 7) & ~7; }
+
+// ---- which kernel a launch gets: spmm_choose() decides, and nothing else does -----------------------------------------------
+// What a launch is, as far as the choice goes.  Plain values: no pointer, nothing of the device.
+struct SpmmLaunchDesc {
+    int x_dtype, y_dtype, feat;
+    int64_t n_rows;
+    bool has_plan;
+    int64_t nnz, n_chunks, n_flat;   // the plan's (0 without one; n_flat = 0: the plan has no flattened schedule)
+    bool weighted;
+    int accumulate;
+    bool gate, aligned16, only_long;
+};
+
+// Tuning knobs (diagnostics; defaults are the shipped configuration).  Set through dgll_hip_debug_tune(key, value).
+struct SpmmTune {
+    int unroll = 4;         // key 0: gathers in flight per lane (2, 4 or 8; 2 / 8 only for the widest variants)
+    int rows_per_wave = 0;  // key 1: 0 = automatic
+    int flags = 0;          // key 2: kSpmmXcdRemap (off: measured slower when degree correlates with row id), kSpmmPrefetchNext
+    int threshold = 0;      // key 3: 0 = plan default (256); read when a plan is created
+    int rowslot = 0;        // key 5: row-per-slot kernel: 0 = automatic, 1 = never, 2 = whenever it applies
+    int flat = 0;           // key 13: flattened kernel: 0 = automatic, 1 = never, 2 = whenever the plan has its schedule
+    int flat_edges = 256;   // key 14: edges per wave of the flattened schedule (read when a plan is created)
+    int rowgroup = 0;       // key 15: row-group kernel: 0 = automatic, 1 = never (the choice before it existed),
+                            //         2 / 4 = wherever it is instantiated, with that many slots per row
+};
+static SpmmTune g_tune;
+
+typedef dgll_spmm_choice SpmmChoice;   // include/dgll_hip.h: dgll_hip_debug_spmm_choice() hands it out as it is
+enum { kSpmmWaveRow = 0, kSpmmRowSlot = 1, kSpmmRowGroup = 2, kSpmmFlat = 3 };   // SpmmChoice::kernel
+
 // upper edges of the row-group kernel's band (edges per row, plan average), rows of 8 and of 16 lanes; lower edge: the row-per-slot
 // kernel's 24.  Measured on MI355X (tools/rowgroup_ab.py --band: the products-sized bench graph, thinned and doubled), bf16,
 // unweighted / weighted, against the wave-per-row kernel; two slots per row beat four everywhere (idle share of the lane groups
@@ -714,117 +676,141 @@ static int ws_ld_for(int feat) { return (feat + 7) & ~7; }
 //   F = 100        -12 /  -9 %  -8 /  -6 %  -6 /  -6 %  -2 /  -2 %  -3 /  -2 %    (two rows per wavefront: little left to share)
 constexpr double kRowGroupMaxAvgLen8 = 100.0, kRowGroupMaxAvgLen16 = 64.0;
 
-// Tuning knobs (diagnostics; defaults are the shipped configuration).  Set through dgll_hip_debug_tune().
-static int g_tune_unroll = 4;        // gathers in flight per lane (2, 4 or 8; 8 only for the widest variants)
-static int g_tune_rows_per_wave = 0; // 0 = automatic
-static int g_tune_flags = 0;         // bit 0: XCD-contiguous row mapping (off: measured slower when degree correlates with row id)
-static int g_tune_threshold = 0;     // 0 = plan default (256)
-static int g_tune_rowslot = 0;       // 0 = automatic choice of the row-per-slot kernel, 1 = never, 2 = whenever it applies
-static int g_tune_flat = 0;          // flattened kernel (spmm_csr_flat_kernel): 0 = automatic, 1 = never, 2 = whenever the plan has its schedule
-static int g_tune_flat_edges = 256;  // edges per wave of the flattened schedule (read when a plan is created)
-static int g_tune_rowgroup = 0;      // row-group kernel (spmm_rowgroup_kernel): 0 = automatic, 1 = never (the choice before it existed),
-                                     // 2 / 4 = wherever it is instantiated, with that many slots per row
-
-template <typename XT, typename YT, int EPV, int LPR, int U>
-static hipError_t launch_u(const SpmmArgs& a, dim3 grid, hipStream_t s) {
-    const bool extra = a.accumulate || a.gate;
-    if constexpr (LPR == 32 && U == 4 && sizeof(XT) == 2 && sizeof(YT) == 2) {
-        if (a.flags & 4) {       // diagnostics (dgll_hip_debug_tune(2, 4)): next-row index prefetch
-            if (a.val) {
-                if (extra) hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, true, U, true, true>), grid, dim3(kBlock), 0, s, a);
-                else hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, true, U, false, true>), grid, dim3(kBlock), 0, s, a);
-            } else {
-                if (extra) hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, false, U, true, true>), grid, dim3(kBlock), 0, s, a);
-                else hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, false, U, false, true>), grid, dim3(kBlock), 0, s, a);
-            }
-            return hipGetLastError();
+// The rule, in the order it is applied (16-byte aligned operands; e = the plan's average edges per row, "infinite" without a plan):
+//   row-per-slot (spmm_rowslot_kernel)   rows of <= 16 lanes and e <= 24, rows of 32 lanes and e <= 4.5
+//   row-group (spmm_rowgroup_kernel)     bf16, no accumulate / gate: rows of 8 lanes and 24 < e <= 100, rows of 16 lanes and
+//                                        24 < e <= 64; two slots per row (4 resp. 2 rows per wavefront at a time)
+//   flattened (spmm_csr_flat_kernel)     fp32 rows of 16 / 32 lanes and e >= 8
+//   wave-per-row (spmm_csr_kernel)       everything else -- all rows of 64 lanes, bf16 rows of 32 (F = 256), the accumulate / gate
+//                                        forms above the row-per-slot band, unaligned operands (EPV = 1, 64 lanes), only_long
+// A pure function of its arguments: callable without a device (dgll_hip_debug_spmm_choice, tests/test_spmm_choice_host.py).
+static SpmmChoice spmm_choose(const SpmmLaunchDesc& d, const SpmmTune& t) {
+    const bool bf = d.x_dtype == DGLL_BF16;
+    SpmmChoice c{};
+    c.kernel = kSpmmWaveRow;
+    c.unroll = 4;
+    c.epv = d.aligned16 ? (bf ? 8 : 4) : 1;
+    const int vecs = (d.feat + c.epv - 1) / c.epv;
+    int lpr = d.aligned16 ? 4 : 64;
+    while (lpr < 64 && lpr < vecs) lpr <<= 1;
+    const double avg_len = d.has_plan ? (double)d.nnz / (double)std::max<int64_t>(d.n_rows, 1) : 1e9;
+    int rpw = 1;
+    if (d.has_plan) {
+        // several rows per wavefront amortise wave start-up and smooth the tail: aim for ~96 KiB of gathered bytes per
+        // wave (measured on the products shapes: 4 rows/wave is 8-18 % faster than 1; tools/spmm_tune.py)
+        const double row_bytes = avg_len * d.feat * (bf ? 2.0 : 4.0);
+        rpw = std::min(std::max(row_bytes > 0 ? (int)(98304.0 / row_bytes) : 8, 1), 8);
+    }
+    // the row-group and the flattened kernel exist at four gathers in flight and without the XCD remap only
+    const bool stock = t.unroll == 4 && !(t.flags & kSpmmXcdRemap);
+    if (d.aligned16 && !d.only_long) {
+        // row-per-slot kernel: SHORT rows (<= 24 edges on average) of at most 16 vectors (F <= 128 bf16).  Measured on MI355X
+        // (tools/rowslot_ab.py): 6.6 edges per row -- the halo halves of an 8-way partition -- F = 47: 1.00 -> 0.47 ms, F = 100 /
+        // 128: -24 %; F = 256 (two slots): +6 %, and at 51 edges per row the wave-per-row kernel wins everywhere (+11 .. +32 %:
+        // a slot walks its row U edges at a time, a whole wavefront 64).
+        // Round 3: at F = 256 (two slots) it wins once rows are VERY short -- 3.2 edges per row, the transposed halo half of an 8-way
+        // partition (678 k rows, 2.1 M edges): 0.49 -> 0.39 ms (tools/scaling_trace.py); hence <= 4.5 edges for 32 lanes per row.
+        if (lpr <= 32 && t.rowslot != 1 && (t.rowslot == 2 || (lpr <= 16 && avg_len <= 24.0) || (lpr == 32 && avg_len <= 4.5))) {
+            c.kernel = kSpmmRowSlot;
+            c.spr = 1;
+        } else if (bf && !d.accumulate && !d.gate && t.rowgroup != 1 && stock && vecs > 4 && vecs <= 16) {
+            // row-group kernel: bf16 rows of 8 lanes (F = 33 .. 64) and of 16 lanes (F = 65 .. 128) ABOVE the row-per-slot band, two
+            // slots per row; plain aggregation only (the accumulate / gate forms stay on the wave-per-row kernel).  Key 15 = 2 / 4
+            // forces it wherever it is instantiated: 8-lane rows with that many slots per row, 16-lane rows with two.
+            if (t.rowgroup == 2 || t.rowgroup == 4) c.spr = lpr == 8 ? t.rowgroup : 2;
+            else if (avg_len > 24.0 && avg_len <= (lpr == 8 ? kRowGroupMaxAvgLen8 : kRowGroupMaxAvgLen16)) c.spr = 2;
+            if (c.spr) c.kernel = kSpmmRowGroup;
         }
+        // The flattened edge-stream kernel.  Measured on the products-sized bench graph (tools/flat_ab.py, E = 256, interleaved):
+        // fp32 F = 100 forward 4.23 -> 3.93 ms (-7 %): chosen for fp32 rows of 16 / 32 lanes; bf16 F = 256 forward 4.35 -> 4.26-4.35,
+        // F = 100 / 128 bf16 +3-4 % slower, the weighted + gated + accumulating transposed pass 5.49 -> 5.85 (73-87 registers: 5-6
+        // wavefronts per SIMD against 8): not chosen for bf16 (key 13 = 2 forces it, 1 disables it).
+        if (c.kernel == kSpmmWaveRow && d.n_flat > 0 && t.flat != 1 && stock && vecs > 8 && vecs <= 32 &&
+            (t.flat == 2 || (!bf && avg_len >= 8.0)))
+            c.kernel = kSpmmFlat;
     }
-    if (a.val) {
-        if (extra) hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, true, U, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, true, U, false>), grid, dim3(kBlock), 0, s, a);
-    } else {
-        if (extra) hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, false, U, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_csr_kernel<XT, YT, EPV, LPR, false, U, false>), grid, dim3(kBlock), 0, s, a);
+    if (c.kernel == kSpmmWaveRow) {
+        if (lpr >= 32 && c.epv > 1 && (t.unroll == 2 || t.unroll == 8)) c.unroll = t.unroll;   // the wide-row variants also exist with other unroll depths
+        c.prefetch = (t.flags & kSpmmPrefetchNext) && lpr == 32 && c.unroll == 4 && bf && d.y_dtype == DGLL_BF16;   // diagnostics: next-row index prefetch
     }
-    return hipGetLastError();
+    c.lpr = lpr;
+    // key 1 replaces the automatic value; without a plan (one row per wavefront) only the row-per-slot kernel has ever honoured it
+    if (t.rows_per_wave > 0 && (d.has_plan || c.kernel == kSpmmRowSlot)) rpw = t.rows_per_wave;
+    // rows a wavefront of the row-per-slot / row-group kernel handles at a time: rows_per_wave is a multiple of it
+    const int rows = c.spr ? kWave / lpr / c.spr : 1;
+    c.rows_per_wave = (rpw + rows - 1) / rows * rows;
+    const int64_t waves = c.kernel == kSpmmFlat ? d.n_flat : (d.n_rows + c.rows_per_wave - 1) / c.rows_per_wave;
+    c.row_blocks = d.only_long ? 0 : (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t chunk_blocks = (d.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
+    c.chunk_blocks = (chunk_blocks + kXcds - 1) / kXcds * kXcds;  // keep (block % 8) == XCD for the row blocks
+    c.grid_y = c.kernel == kSpmmRowGroup ? 1 : (vecs + lpr - 1) / lpr;
+    return c;
 }
 
-template <typename XT, typename YT, int EPV, int LPR>
-static hipError_t launch_variant(const SpmmArgs& a, dim3 grid, hipStream_t s) {
-    if constexpr (LPR >= 32 && EPV > 1) {  // the wide-row variants also exist with other unroll depths
-        if (g_tune_unroll == 8) return launch_u<XT, YT, EPV, LPR, 8>(a, grid, s);
-        if (g_tune_unroll == 2) return launch_u<XT, YT, EPV, LPR, 2>(a, grid, s);
-    }
-    return launch_u<XT, YT, EPV, LPR, 4>(a, grid, s);
+// ---- launch: runtime values -> template arguments, one dispatch per kernel family ---------------------------------------------
+// Only what spmm_choose() can return is instantiated (the device code object holds 208 row kernels, not the cross product).
+template <typename F> static hipError_t with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+// f(std::integral_constant<int, V>) for the V of the list that equals v: the || fold stops at the first match (its f's result is
+// kept in r); a v outside the list reaches no f and is an error -- no kernel is instantiated for it
+template <int... Vs, typename F> static hipError_t with_int(int v, F&& f) {
+    hipError_t r = hipErrorInvalidValue;
+    (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return r;
 }
 
-template <typename XT, typename YT, int EPV, int LPR>
-static hipError_t launch_rowslot(const SpmmArgs& a, dim3 grid, hipStream_t s) {
-    const bool extra = a.accumulate || a.gate;
-    if (a.val) {
-        if (extra) hipLaunchKernelGGL((spmm_rowslot_kernel<XT, YT, EPV, LPR, true, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_rowslot_kernel<XT, YT, EPV, LPR, true, false>), grid, dim3(kBlock), 0, s, a);
-    } else {
-        if (extra) hipLaunchKernelGGL((spmm_rowslot_kernel<XT, YT, EPV, LPR, false, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_rowslot_kernel<XT, YT, EPV, LPR, false, false>), grid, dim3(kBlock), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-template <typename XT, typename YT, int EPV>
-static hipError_t launch_rowslot_lpr(const SpmmArgs& a, int lpr, dim3 grid, hipStream_t s) {
-    switch (lpr) {
-        case 4: return launch_rowslot<XT, YT, EPV, 4>(a, grid, s);
-        case 8: return launch_rowslot<XT, YT, EPV, 8>(a, grid, s);
-        case 16: return launch_rowslot<XT, YT, EPV, 16>(a, grid, s);
-        default: return launch_rowslot<XT, YT, EPV, 32>(a, grid, s);
-    }
-}
-
-template <typename XT, typename YT, int EPV, int LPR, int SPR>
-static hipError_t launch_rowgroup(const SpmmArgs& a, dim3 grid, hipStream_t s) {
-    if (a.val) hipLaunchKernelGGL((spmm_rowgroup_kernel<XT, YT, EPV, LPR, SPR, true>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((spmm_rowgroup_kernel<XT, YT, EPV, LPR, SPR, false>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-// instantiated for bf16 rows of 8 lanes (2 or 4 slots per row) and of 16 lanes (2 slots per row)
-template <typename YT>
-static hipError_t launch_rowgroup_lpr(const SpmmArgs& a, int lpr, int spr, dim3 grid, hipStream_t s) {
-    if (lpr == 16) return launch_rowgroup<bf16_t, YT, 8, 16, 2>(a, grid, s);
-    if (spr == 4) return launch_rowgroup<bf16_t, YT, 8, 8, 4>(a, grid, s);
-    return launch_rowgroup<bf16_t, YT, 8, 8, 2>(a, grid, s);
-}
-
-template <typename XT, typename YT, int EPV, int LPR>
-static hipError_t launch_flat(const SpmmArgs& a, dim3 grid, hipStream_t s) {
-    const bool extra = a.accumulate || a.gate;
-    if (a.val) {
-        if (extra) hipLaunchKernelGGL((spmm_csr_flat_kernel<XT, YT, EPV, LPR, true, 4, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_csr_flat_kernel<XT, YT, EPV, LPR, true, 4, false>), grid, dim3(kBlock), 0, s, a);
-    } else {
-        if (extra) hipLaunchKernelGGL((spmm_csr_flat_kernel<XT, YT, EPV, LPR, false, 4, true>), grid, dim3(kBlock), 0, s, a);
-        else hipLaunchKernelGGL((spmm_csr_flat_kernel<XT, YT, EPV, LPR, false, 4, false>), grid, dim3(kBlock), 0, s, a);
-    }
+static hipError_t launch(void (*kernel)(const SpmmArgs), const SpmmArgs& a, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 
 template <typename XT, typename YT, int EPV>
-static hipError_t launch_flat_lpr(const SpmmArgs& a, int lpr, dim3 grid, hipStream_t s) {
-    if (lpr == 16) return launch_flat<XT, YT, EPV, 16>(a, grid, s);
-    return launch_flat<XT, YT, EPV, 32>(a, grid, s);
+static hipError_t launch_rows(const SpmmChoice& c, bool weighted, bool extra, const SpmmArgs& a, dim3 grid, hipStream_t s) {
+    return with_bool(weighted, [&](auto V) { return with_bool(extra, [&](auto E) {
+        constexpr bool HV = decltype(V)::value, EX = decltype(E)::value;
+        // compile time first: operands that are not 16-byte aligned have one kernel (one element per lane, 64 lanes per row);
+        // the else arm is the RUNTIME choice among the 16-byte families and is not instantiated at EPV = 1
+        if constexpr (EPV == 1) {
+            return launch(spmm_csr_kernel<XT, YT, 1, 64, HV, 4, EX>, a, grid, s);
+        } else if (c.kernel == kSpmmRowSlot) {
+            return with_int<4, 8, 16, 32>(c.lpr, [&](auto L) {
+                return launch(spmm_rowslot_kernel<XT, YT, EPV, decltype(L)::value, HV, EX>, a, grid, s);
+            });
+        } else if (c.kernel == kSpmmRowGroup) {   // bf16 rows of 8 lanes (2 or 4 slots per row) and of 16 lanes (2 slots per row)
+            if constexpr (sizeof(XT) == 2 && !EX) {
+                if (c.lpr == 16) return launch(spmm_rowgroup_kernel<XT, YT, EPV, 16, 2, HV>, a, grid, s);
+                if (c.spr == 4) return launch(spmm_rowgroup_kernel<XT, YT, EPV, 8, 4, HV>, a, grid, s);
+                return launch(spmm_rowgroup_kernel<XT, YT, EPV, 8, 2, HV>, a, grid, s);
+            }
+            return hipErrorInvalidValue;
+        } else if (c.kernel == kSpmmFlat) {
+            return with_int<16, 32>(c.lpr, [&](auto L) {
+                return launch(spmm_csr_flat_kernel<XT, YT, EPV, decltype(L)::value, HV, 4, EX>, a, grid, s);
+            });
+        } else {
+            return with_int<4, 8, 16, 32, 64>(c.lpr, [&](auto L) {
+                constexpr int LPR = decltype(L)::value;
+                if constexpr (LPR >= 32) {
+                    if (c.unroll == 8) return launch(spmm_csr_kernel<XT, YT, EPV, LPR, HV, 8, EX>, a, grid, s);
+                    if (c.unroll == 2) return launch(spmm_csr_kernel<XT, YT, EPV, LPR, HV, 2, EX>, a, grid, s);
+                }
+                if constexpr (LPR == 32 && sizeof(XT) == 2 && sizeof(YT) == 2) {
+                    if (c.prefetch) return launch(spmm_csr_kernel<XT, YT, EPV, LPR, HV, 4, EX, true>, a, grid, s);
+                }
+                return launch(spmm_csr_kernel<XT, YT, EPV, LPR, HV, 4, EX>, a, grid, s);
+            });
+        }
+    }); });
 }
 
-template <typename XT, typename YT, int EPV>
-static hipError_t launch_lpr(const SpmmArgs& a, int lpr, dim3 grid, hipStream_t s) {
-    switch (lpr) {
-        case 4: return launch_variant<XT, YT, EPV, 4>(a, grid, s);
-        case 8: return launch_variant<XT, YT, EPV, 8>(a, grid, s);
-        case 16: return launch_variant<XT, YT, EPV, 16>(a, grid, s);
-        case 32: return launch_variant<XT, YT, EPV, 32>(a, grid, s);
-        default: return launch_variant<XT, YT, EPV, 64>(a, grid, s);
-    }
+static hipError_t spmm_launch(const SpmmLaunchDesc& d, const SpmmChoice& c, const SpmmArgs& a, hipStream_t s) {
+    const dim3 grid((uint32_t)(c.row_blocks + c.chunk_blocks), (uint32_t)c.grid_y);
+    const bool extra = d.accumulate || d.gate;
+    return with_bool(c.epv > 1, [&](auto V) {
+        constexpr bool vec = decltype(V)::value;
+        if (d.x_dtype == DGLL_F32) return launch_rows<float, float, vec ? 4 : 1>(c, d.weighted, extra, a, grid, s);
+        if (d.y_dtype == DGLL_BF16) return launch_rows<bf16_t, bf16_t, vec ? 8 : 1>(c, d.weighted, extra, a, grid, s);
+        return launch_rows<bf16_t, float, vec ? 8 : 1>(c, d.weighted, extra, a, grid, s);
+    });
 }
 
 }  // namespace dgll
@@ -839,7 +825,7 @@ DGLL_API int dgll_hip_csr_plan_create(void* stream, const int64_t* rowptr, int64
     dgll_csr_plan* p = new dgll_csr_plan();
     p->n_rows = n_rows;
     p->nnz = nnz;
-    p->threshold = long_row_threshold > 0 ? long_row_threshold : (g_tune_threshold > 0 ? g_tune_threshold : 256);
+    p->threshold = long_row_threshold > 0 ? long_row_threshold : (g_tune.threshold > 0 ? g_tune.threshold : 256);
     hipError_t e = hipGetDevice(&p->device);
     if (e != hipSuccess) { delete p; return hip_fail(e, "hipGetDevice"); }
     if (long_row_threshold < 0) {   // caller's guarantee: no row is longer than the default threshold (e.g. a sampled block with
@@ -911,8 +897,8 @@ DGLL_API int dgll_hip_csr_plan_create(void* stream, const int64_t* rowptr, int64
         PLAN_TRY(hipStreamSynchronize(s));
     }
     // the flattened kernel's wave schedule (one binary search per wave, once per graph)
-    if (n_rows > 0 && g_tune_flat_edges > 0) {
-        p->flat_edges = g_tune_flat_edges;
+    if (n_rows > 0 && g_tune.flat_edges > 0) {
+        p->flat_edges = g_tune.flat_edges;
         p->n_flat = (nnz + kFlatRowCost * n_rows + p->flat_edges - 1) / p->flat_edges;
         PLAN_TRY(hipMalloc(&p->d_flat_row0, sizeof(int64_t) * (size_t)(p->n_flat + 1)));
         const int blocks = (int)std::min<int64_t>((p->n_flat + 1 + kBlock - 1) / kBlock, 4096);
@@ -934,21 +920,33 @@ extern int g_tune_loader_blocks_per_cu;   // gather.hip
 
 DGLL_API int dgll_hip_debug_tune(int key, int value) {
     switch (key) {
-        case 0: g_tune_unroll = value; break;
-        case 1: g_tune_rows_per_wave = value; break;
-        case 2: g_tune_flags = value; break;
-        case 3: g_tune_threshold = value; break;
+        case 0: g_tune.unroll = value; break;
+        case 1: g_tune.rows_per_wave = value; break;
+        case 2: g_tune.flags = value; break;
+        case 3: g_tune.threshold = value; break;
         case 4: g_tune_mfma_kperm = value; break;
-        case 5: g_tune_rowslot = value; break;
-        case 13: g_tune_flat = value; break;
-        case 14: g_tune_flat_edges = value; break;
-        case 15: g_tune_rowgroup = value; break;
+        case 5: g_tune.rowslot = value; break;
+        case 13: g_tune.flat = value; break;
+        case 14: g_tune.flat_edges = value; break;
+        case 15: g_tune.rowgroup = value; break;
         case 7: break;                              // (retired: unroll depth of the first-generation GAT backward passes)
         case 9: g_tune_gat_gen = value; break;
         case 11: g_tune_res_per_cu = value; break;
         case 12: g_tune_loader_blocks_per_cu = value; break;
         default: set_error("unknown tuning key"); return DGLL_ERR_INVALID;
     }
+    return DGLL_OK;
+}
+
+DGLL_API int dgll_hip_debug_spmm_choice(int x_dtype, int y_dtype, int feat, int64_t n_rows, int has_plan, int64_t nnz, int64_t n_chunks,
+                                        int64_t n_flat, int weighted, int accumulate, int gate, int aligned16, int only_long,
+                                        dgll_spmm_choice* out) {
+    DGLL_REQUIRE(out != nullptr, "out is NULL");
+    DGLL_REQUIRE((x_dtype == DGLL_F32 || x_dtype == DGLL_BF16) && (y_dtype == DGLL_F32 || y_dtype == DGLL_BF16), "dtype");
+    DGLL_REQUIRE(feat > 0 && n_rows > 0 && nnz >= 0 && n_chunks >= 0 && n_flat >= 0, "bad launch description");
+    const bool plan = has_plan != 0;
+    *out = spmm_choose(SpmmLaunchDesc{x_dtype, y_dtype, feat, n_rows, plan, plan ? nnz : 0, plan ? n_chunks : 0, plan ? n_flat : 0,
+                                      weighted != 0, accumulate, gate != 0, aligned16 != 0, only_long != 0}, g_tune);
     return DGLL_OK;
 }
 
@@ -1028,8 +1026,7 @@ int dgll_spmm_csr_impl(void* stream, const dgll_csr_plan* plan, const int64_t* r
     a.rowptr = rowptr; a.col = col; a.val = val; a.X = X; a.Y = Y;
     a.ldx = ldx; a.ldy = ldy; a.n_rows = n_rows; a.feat = feat; a.reduce = reduce; a.epilogue = epilogue; a.bias = bias;
     a.ws_ld = ws_ld_for(feat);
-    a.rows_per_wave = 1;
-    a.flags = g_tune_flags;
+    a.flags = g_tune.flags;
     a.row_scale = row_scale;
     a.accumulate = accumulate;
     a.gate = gate; a.ldg = ldg;
@@ -1047,124 +1044,24 @@ int dgll_spmm_csr_impl(void* stream, const dgll_csr_plan* plan, const int64_t* r
             }
             a.ws = static_cast<float*>(workspace);
         }
-        // several rows per wavefront amortise wave start-up and smooth the tail: aim for ~96 KiB of gathered bytes per
-        // wave (measured on the products shapes: 4 rows/wave is 8-18 % faster than 1; tools/spmm_tune.py)
-        const double row_bytes = (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) * feat *
-                                 (x_dtype == DGLL_BF16 ? 2.0 : 4.0);
-        int rpw = row_bytes > 0 ? (int)(98304.0 / row_bytes) : 8;
-        a.rows_per_wave = std::min(std::max(rpw, 1), 8);
-        if (g_tune_rows_per_wave > 0) a.rows_per_wave = g_tune_rows_per_wave;
     }
     if (only_long && (!plan || plan->n_long == 0)) return DGLL_OK;
-    const int64_t waves = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
-    const int64_t row_blocks = only_long ? 0 : (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    int64_t chunk_blocks = (a.n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
-    chunk_blocks = (chunk_blocks + kXcds - 1) / kXcds * kXcds;  // keep (block % 8) == XCD for the row blocks
-    DGLL_REQUIRE(row_blocks + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
-    a.row_blocks = (uint32_t)row_blocks;
-    a.chunk_blocks = (uint32_t)chunk_blocks;
-
     const int esz = x_dtype == DGLL_BF16 ? 2 : 4;
     const int ysz = y_dtype == DGLL_BF16 ? 2 : 4;
-    const int epv = 16 / esz;
     const bool fast = aligned16(X) && aligned16(Y) && (ldx * esz) % 16 == 0 && (ldy * ysz) % 16 == 0 &&
-                      ((int64_t)epv * ysz) % 16 == 0 && (!gate || (aligned16(gate) && (ldg * ysz) % 16 == 0));
-    if (fast) a.flags |= 2;
-    hipError_t err;
-    bool rowslot = false;
-    if (fast) {
-        const int vecs = (feat + epv - 1) / epv;
-        int lpr = 4;
-        while (lpr < 64 && lpr < vecs) lpr <<= 1;
-        // row-per-slot kernel: SHORT rows (<= 24 edges on average) of at most 16 vectors (F <= 128 bf16).  Measured on MI355X
-        // (tools/rowslot_ab.py): 6.6 edges per row -- the halo halves of an 8-way partition -- F = 47: 1.00 -> 0.47 ms, F = 100 /
-        // 128: -24 %; F = 256 (two slots): +6 %, and at 51 edges per row the wave-per-row kernel wins everywhere (+11 .. +32 %:
-        // a slot walks its row U edges at a time, a whole wavefront 64).
-        const double avg_len = plan ? (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) : 1e9;
-        // Round 3: at F = 256 (two slots) it wins once rows are VERY short -- 3.2 edges per row, the transposed halo half of an 8-way
-        // partition (678 k rows, 2.1 M edges): 0.49 -> 0.39 ms (tools/scaling_trace.py); hence <= 4.5 edges for 32 lanes per row.
-        rowslot = !only_long && lpr <= 32 && g_tune_rowslot != 1 &&
-                  (g_tune_rowslot == 2 || (lpr <= 16 && avg_len <= 24.0) || (lpr == 32 && avg_len <= 4.5));
-        if (rowslot) {
-            const int slots = kWave / lpr;
-            a.rows_per_wave = std::max(a.rows_per_wave, 1);
-            a.rows_per_wave = (a.rows_per_wave + slots - 1) / slots * slots;
-            if (g_tune_rows_per_wave > 0) a.rows_per_wave = (g_tune_rows_per_wave + slots - 1) / slots * slots;
-        }
-    }
-    // row-group kernel: bf16 rows of 8 lanes (F = 33 .. 64) and of 16 lanes (F = 65 .. 128) ABOVE the row-per-slot band, two slots
-    // per row (band edges and measurements: kRowGroupMaxAvgLen8 / 16 above); plain aggregation only
-    // (the accumulate / gate forms stay on the wave-per-row kernel).  dgll_hip_debug_tune(15, 1) gives the choice before this kernel
-    // existed, (15, 2) / (15, 4) force it wherever it is instantiated (16-lane rows included) with that many slots per row.
-    int rowgroup_spr = 0;
-    if (fast && !rowslot && !only_long && x_dtype == DGLL_BF16 && !accumulate && !gate && g_tune_rowgroup != 1 &&
-        g_tune_unroll == 4 && !(a.flags & 1)) {
-        const int vecs = (feat + epv - 1) / epv;
-        const double avg_len = plan ? (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) : 1e9;
-        if (g_tune_rowgroup == 2 || g_tune_rowgroup == 4) {
-            if (vecs > 4 && vecs <= 8) rowgroup_spr = g_tune_rowgroup;
-            else if (vecs > 8 && vecs <= 16) rowgroup_spr = 2;
-        } else if (avg_len > 24.0 && ((vecs > 4 && vecs <= 8 && avg_len <= kRowGroupMaxAvgLen8) ||
-                                      (vecs > 8 && vecs <= 16 && avg_len <= kRowGroupMaxAvgLen16))) {
-            rowgroup_spr = 2;
-        }
-    }
-    if (rowgroup_spr) {
-        const int vecs = (feat + epv - 1) / epv;
-        const int lpr = vecs <= 8 ? 8 : 16;
-        const int rows = kWave / lpr / rowgroup_spr;           // rows per wavefront at a time
-        a.rows_per_wave = (std::max(a.rows_per_wave, 1) + rows - 1) / rows * rows;
-        const int64_t waves2 = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
-        const int64_t row_blocks2 = (waves2 + kWavesPerBlock - 1) / kWavesPerBlock;
-        DGLL_REQUIRE(row_blocks2 + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
-        a.row_blocks = (uint32_t)row_blocks2;
-        dim3 grid((uint32_t)(row_blocks2 + chunk_blocks), 1u);
-        if (y_dtype == DGLL_BF16) err = launch_rowgroup_lpr<bf16_t>(a, lpr, rowgroup_spr, grid, s);
-        else err = launch_rowgroup_lpr<float>(a, lpr, rowgroup_spr, grid, s);
-    } else if (rowslot) {   // the grid depends on rows_per_wave: recompute
-        const int64_t waves2 = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
-        const int64_t row_blocks2 = (waves2 + kWavesPerBlock - 1) / kWavesPerBlock;
-        DGLL_REQUIRE(row_blocks2 + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
-        a.row_blocks = (uint32_t)row_blocks2;
-        const int vecs = (feat + epv - 1) / epv;
-        int lpr = 4;
-        while (lpr < 64 && lpr < vecs) lpr <<= 1;
-        dim3 grid((uint32_t)(row_blocks2 + chunk_blocks), (uint32_t)((vecs + lpr - 1) / lpr));
-        if (x_dtype == DGLL_F32) err = launch_rowslot_lpr<float, float, 4>(a, lpr, grid, s);
-        else if (y_dtype == DGLL_BF16) err = launch_rowslot_lpr<bf16_t, bf16_t, 8>(a, lpr, grid, s);
-        else err = launch_rowslot_lpr<bf16_t, float, 8>(a, lpr, grid, s);
-    } else if (fast && !only_long && plan && plan->d_flat_row0 && g_tune_flat != 1 && g_tune_unroll == 4 && !(a.flags & 1) &&
-               [&]() { const int v = (feat + epv - 1) / epv; return v > 8 && v <= 32; }() &&
-               (g_tune_flat == 2 || (x_dtype == DGLL_F32 && (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) >= 8.0))) {
-        // The flattened edge-stream kernel.  Measured on the products-sized bench graph (tools/flat_ab.py, E = 256, interleaved):
-        // fp32 F = 100 forward 4.23 -> 3.93 ms (-7 %): chosen for fp32 rows of 16 / 32 lanes; bf16 F = 256 forward 4.35 -> 4.26-4.35,
-        // F = 100 / 128 bf16 +3-4 % slower, the weighted + gated + accumulating transposed pass 5.49 -> 5.85 (73-87 registers: 5-6
-        // wavefronts per SIMD against 8): not chosen for bf16 (dgll_hip_debug_tune(13, 2) forces it, (13, 1) disables it).
-        const int vecs = (feat + epv - 1) / epv;
-        const int lpr = vecs <= 16 ? 16 : 32;
-        a.flat_row0 = plan->d_flat_row0;
-        a.n_flat = plan->n_flat;
-        const int64_t flat_blocks = (plan->n_flat + kWavesPerBlock - 1) / kWavesPerBlock;
-        DGLL_REQUIRE(flat_blocks + chunk_blocks < (int64_t)0x7fffffff, "grid too large");
-        a.row_blocks = (uint32_t)flat_blocks;
-        dim3 grid((uint32_t)(flat_blocks + chunk_blocks), (uint32_t)((vecs + lpr - 1) / lpr));
-        if (x_dtype == DGLL_F32) err = launch_flat_lpr<float, float, 4>(a, lpr, grid, s);
-        else if (y_dtype == DGLL_BF16) err = launch_flat_lpr<bf16_t, bf16_t, 8>(a, lpr, grid, s);
-        else err = launch_flat_lpr<bf16_t, float, 8>(a, lpr, grid, s);
-    } else if (fast) {
-        const int vecs = (feat + epv - 1) / epv;
-        int lpr = 4;
-        while (lpr < 64 && lpr < vecs) lpr <<= 1;
-        dim3 grid((uint32_t)(row_blocks + chunk_blocks), (uint32_t)((vecs + lpr - 1) / lpr));
-        if (x_dtype == DGLL_F32) err = launch_lpr<float, float, 4>(a, lpr, grid, s);
-        else if (y_dtype == DGLL_BF16) err = launch_lpr<bf16_t, bf16_t, 8>(a, lpr, grid, s);
-        else err = launch_lpr<bf16_t, float, 8>(a, lpr, grid, s);
-    } else {
-        dim3 grid((uint32_t)(row_blocks + chunk_blocks), (uint32_t)((feat + 63) / 64));
-        if (x_dtype == DGLL_F32) err = launch_variant<float, float, 1, 64>(a, grid, s);
-        else if (y_dtype == DGLL_BF16) err = launch_variant<bf16_t, bf16_t, 1, 64>(a, grid, s);
-        else err = launch_variant<bf16_t, float, 1, 64>(a, grid, s);
-    }
+                      (!gate || (aligned16(gate) && (ldg * ysz) % 16 == 0));
+    if (fast) a.flags |= kSpmmAligned16;
+
+    const SpmmLaunchDesc d{x_dtype, y_dtype, feat, n_rows, plan != nullptr, plan ? plan->nnz : 0, plan ? plan->n_chunks : 0,
+                           plan && plan->d_flat_row0 ? plan->n_flat : 0, val != nullptr, accumulate, gate != nullptr, fast,
+                           only_long != 0};
+    const SpmmChoice c = spmm_choose(d, g_tune);
+    DGLL_REQUIRE(c.row_blocks + c.chunk_blocks < (int64_t)0x7fffffff, "grid too large");
+    a.rows_per_wave = c.rows_per_wave;
+    a.row_blocks = (uint32_t)c.row_blocks;
+    a.chunk_blocks = (uint32_t)c.chunk_blocks;
+    if (c.kernel == kSpmmFlat) { a.flat_row0 = plan->d_flat_row0; a.n_flat = plan->n_flat; }
+    hipError_t err = spmm_launch(d, c, a, s);
     if (err != hipSuccess) return hip_fail(err, "spmm_csr_kernel launch");
 
     if (plan && plan->n_long > 0) {

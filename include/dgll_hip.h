@@ -50,6 +50,19 @@ int dgll_hip_device_info(int device, char* name, int name_len, int* compute_unit
  * 3 default long-row threshold).  Not part of the data path; not thread-safe. */
 int dgll_hip_debug_tune(int key, int value);
 
+/* Diagnostics only, touches no device: the kernel a dgll_hip_spmm_csr* launch of this description gets under the current
+ * knobs -- the launch path calls the same function.  kernel: 0 wave-per-row, 1 row-per-slot, 2 row-group, 3 flattened;
+ * epv / lpr: elements per lane and lanes per row; spr: slots per row (0 for kernels 0 and 3); unroll / prefetch: gathers in
+ * flight per lane and the next-row index prefetch; the grid is (row_blocks + chunk_blocks, grid_y).  nnz / n_chunks /
+ * n_flat are the plan's (ignored when has_plan is 0; n_flat = 0: no flattened schedule).                           */
+struct dgll_spmm_choice {
+    int kernel, epv, lpr, spr, unroll, prefetch, rows_per_wave, grid_y;
+    int64_t row_blocks, chunk_blocks;
+};
+int dgll_hip_debug_spmm_choice(int x_dtype, int y_dtype, int feat, int64_t n_rows, int has_plan, int64_t nnz,
+                               int64_t n_chunks, int64_t n_flat, int weighted, int accumulate, int gate, int aligned16,
+                               int only_long, struct dgll_spmm_choice* out);
+
 /* ---- CSR schedule ----------------------------------------------------------------------------------
  * Built once per adjacency structure (the reference builds its adjacency once per graph,
  * nn/utils/utils.py:171,179).  Rows longer than `long_row_threshold` nonzeros (<= 0 selects the default,
