@@ -779,8 +779,9 @@ static int gat_common(EdgeArgs& a, const int64_t* rowptr, const int32_t* col, in
 }
 
 // Launch geometry of the second-generation kernels (gat_kernel.hpp): `nh` heads per wavefront on `lpr` = nh * lanes-per-head
-// lanes per row.  They cover sparseGatConv's form -- exp(-leakyrelu), no max subtraction, no attention-dropout multipliers --
-// for any per-head width that is a multiple of the 16-byte vector.  False: the first-generation kernels run.
+// lanes per row.  They cover sparseGatConv's form -- exp(-leakyrelu), no max subtraction, no attention-dropout multiplier ARRAY
+// (dropout drawn in the kernel is theirs: the *_dropout entry points) -- for any per-head width that is a multiple of the 16-byte
+// vector.  False: the first-generation kernels run.
 static bool gat2_pick(const EdgeArgs& a, int* lpr, int* nh, uint32_t* grid_y) {
     if (g_tune_gat_gen == 1 || a.edge_scale || a.use_max || a.M) return false;
     int lph = 1;
@@ -800,6 +801,18 @@ static bool gat2_pick(const EdgeArgs& a, int* lpr, int* nh, uint32_t* grid_y) {
     while (n * lph < 4) lph <<= 1;                           // at least 4 lanes per row slot (idle lanes inside a head)
     *lpr = n * lph; *nh = n; *grid_y = (uint32_t)((a.heads + n - 1) / n);
     return true;
+}
+
+// In-kernel attention dropout (the *_dropout entry points): p in [0, 1) and the device pointer to the two seed words.
+static int gat_drop_args(EdgeArgs& a, double p, const uint32_t* seed) {
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("attention dropout: p must lie in [0, 1)");
+        return DGLL_ERR_INVALID;
+    }
+    DGLL_REQUIRE(seed, "attention dropout needs the device pointer to its two 32-bit seed words");
+    DGLL_REQUIRE(a.n_rows < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
+    a.drop_p = (float)p; a.drop = gat_dropout_params(p); a.drop_seed = seed;
+    return DGLL_OK;
 }
 
 // One head whose gathered-side scores sit right behind the last column of the gathered rows (same stride): the gather itself
@@ -837,7 +850,7 @@ static int gat_fwd_impl(void* stream, const dgll_csr_plan* plan, const int64_t* 
                         const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* edge_scale, void* out,
                         int64_t ldo, int dtype, float* rowsum, float* rowmax, int64_t n_rows, int heads, int fo,
                         float alpha, int apply_elu, int mode, void* workspace, size_t workspace_bytes, int raw, int accumulate,
-                        const float* attn2 = nullptr) {
+                        const float* attn2 = nullptr, bool drop = false, double drop_p = 0.0, const uint32_t* drop_seed = nullptr) {
     if (n_rows <= 0) return DGLL_OK;
     EdgeArgs a{};
     int rc = gat_common(a, rowptr, col, n_rows, heads, fo, dtype, alpha, mode, apply_elu);
@@ -845,6 +858,11 @@ static int gat_fwd_impl(void* stream, const dgll_csr_plan* plan, const int64_t* 
     DGLL_REQUIRE(H && S && (T || attn2) && out && rowsum, "NULL argument");
     DGLL_REQUIRE(!attn2 || (!T && mode == 0 && !edge_scale), "the row-score form takes a2 INSTEAD of T (sparseGatConv's form, no attention dropout)");
     a.attn2 = attn2;
+    if (drop) {
+        DGLL_REQUIRE(mode == 0 && !edge_scale && !raw && !accumulate, "in-kernel dropout: sparseGatConv's form, one launch over the rows");
+        rc = gat_drop_args(a, drop_p, drop_seed);
+        if (rc != DGLL_OK) return rc;
+    }
     DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs a rowmax output");
     const int esz = dtype == DGLL_BF16 ? 2 : 4, epv = 16 / esz;
     DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && ldh >= a.feat && ldo >= a.feat, "H/out must be 16-byte aligned");
@@ -857,7 +875,12 @@ static int gat_fwd_impl(void* stream, const dgll_csr_plan* plan, const int64_t* 
     if (rc != DGLL_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int lpr, nh, lph;
-    if (attn2) {
+    if (drop) {
+        if (!gat2_pick(a, &lpr, &nh, &grid.y) || !(attn2 ? gat2_launch_0rd(dtype, lpr, nh, grid, s, a) : gat2_launch_0d(dtype, lpr, nh, grid, s, a))) {
+            set_error("no second-generation GAT kernel with dropout for this head layout");
+            return DGLL_ERR_UNSUPPORTED;
+        }
+    } else if (attn2) {
         if (!gat2_pick(a, &lpr, &nh, &grid.y) || !gat2_launch_0r(dtype, lpr, nh, grid, s, a)) {
             set_error("no row-score GAT kernel for this head layout");
             return DGLL_ERR_UNSUPPORTED;
@@ -924,7 +947,7 @@ static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int6
                              const float* rowsum, const float* rowmax, void* dn, int64_t ldn, float* dd, float* sd_out,
                              int sd_stride, float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu,
                              int mode, int accumulate, void* workspace, size_t workspace_bytes, float* part3 = nullptr,
-                             const float* attn2 = nullptr) {
+                             const float* attn2 = nullptr, bool drop = false, double drop_p = 0.0, const uint32_t* drop_seed = nullptr) {
     if (n_rows <= 0) return DGLL_OK;
     EdgeArgs a{};
     int rc = gat_common(a, rowptr, col, n_rows, heads, fo, dtype, alpha, mode, apply_elu);
@@ -933,6 +956,11 @@ static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int6
     DGLL_REQUIRE(!attn2 || (!T && mode == 0 && !edge_scale && accumulate == 3),
                  "the row-score form takes a2 INSTEAD of T: sparseGatConv's form, one launch over the rows (exact dd_i)");
     a.attn2 = attn2;
+    if (drop) {
+        DGLL_REQUIRE(mode == 0 && !edge_scale && accumulate == 3, "in-kernel dropout: sparseGatConv's form, one launch over the rows (exact dd_i)");
+        rc = gat_drop_args(a, drop_p, drop_seed);
+        if (rc != DGLL_OK) return rc;
+    }
     DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs the forward's rowmax");
     const int esz = dtype == DGLL_BF16 ? 2 : 4, epv = 16 / esz;
     DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && vec_ok(grad_out, ldg, esz) && vec_ok(dn, ldn, esz),
@@ -955,11 +983,12 @@ static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int6
         a.part3 = part3;
         a.accumulate = accumulate == 1 ? 1 : 0;
         const bool inrow = !attn2 && gat2_inrow(a, lpr, nh, esz, a.T, nullptr);
-        const bool ok = attn2 ? gat2_launch_3r(dtype, lpr, nh, grid, s, a)
+        const bool ok = drop ? (attn2 ? gat2_launch_3rd(dtype, lpr, nh, grid, s, a) : gat2_launch_3d(dtype, lpr, nh, grid, s, a))
+                      : attn2 ? gat2_launch_3r(dtype, lpr, nh, grid, s, a)
                               : (a.exact_dd ? gat2_launch_3(dtype, lpr, nh, grid, s, a, inrow) : gat2_launch_1(dtype, lpr, nh, grid, s, a, inrow));
         if (!ok) { set_error("no second-generation GAT kernel for this head layout"); return DGLL_ERR_UNSUPPORTED; }
     } else {
-        DGLL_REQUIRE(!attn2, "the row-score form needs the second-generation kernels");
+        DGLL_REQUIRE(!attn2 && !drop, "the row-score form and in-kernel dropout need the second-generation kernels");
         rc = gat1_pick(a, epv, &lph, &lpr, &grid.y);
         if (rc != DGLL_OK) return rc;
         DGLL_REQUIRE(dd, "the first-generation rows pass writes dd");
@@ -1009,7 +1038,8 @@ static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const in
                              const float* edge_scale, void* grad_H, int64_t ldgh, float* grad_T, int dtype,
                              int64_t n_rows_t, int heads, int fo, float alpha, int mode, void* workspace,
                              size_t workspace_bytes, const float* attn1 = nullptr, const float* attn2 = nullptr,
-                             const float* grad_S_rows = nullptr) {
+                             const float* grad_S_rows = nullptr, bool drop = false, double drop_p = 0.0,
+                             const uint32_t* drop_seed = nullptr) {
     if (n_rows_t <= 0) return DGLL_OK;
     EdgeArgs t{};
     int rc = gat_common(t, t_rowptr, t_col, n_rows_t, heads, fo, dtype, alpha, mode, 0);
@@ -1024,6 +1054,11 @@ static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const in
     t.tstride = col_stride > 0 ? col_stride : heads;
     DGLL_REQUIRE(!attn1 || (attn2 && grad_S_rows), "the score-gradient epilogue needs a1, a2 and the rows' grad_S");
     t.attn1 = attn1; t.attn2 = attn2; t.gs_rows = grad_S_rows;
+    if (drop) {
+        DGLL_REQUIRE(mode == 0 && !edge_scale, "in-kernel dropout: sparseGatConv's form");
+        rc = gat_drop_args(t, drop_p, drop_seed);
+        if (rc != DGLL_OK) return rc;
+    }
     t.M = mode == 1 ? rowmax_col : nullptr; t.edge_scale = edge_scale; t.Y = grad_H; t.ldy = ldgh; t.out_a = grad_T;
     t.out_b = nullptr;
     dim3 grid(1, 1, 1);
@@ -1031,7 +1066,12 @@ static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const in
     if (rc != DGLL_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int lpr, nh, lph;
-    if (gat2_pick(t, &lpr, &nh, &grid.y)) {
+    if (drop) {
+        if (!gat2_pick(t, &lpr, &nh, &grid.y) || !gat2_launch_2d(dtype, lpr, nh, grid, s, t)) {
+            set_error("no second-generation GAT kernel with dropout for this head layout");
+            return DGLL_ERR_UNSUPPORTED;
+        }
+    } else if (gat2_pick(t, &lpr, &nh, &grid.y)) {
         if (!gat2_launch_2(dtype, lpr, nh, grid, s, t, gat2_inrow(t, lpr, nh, esz, t.T, t.DD))) { set_error("no second-generation GAT kernel for this head layout"); return DGLL_ERR_UNSUPPORTED; }
     } else {
         rc = gat1_pick(t, epv, &lph, &lpr, &grid.y);
@@ -1122,6 +1162,106 @@ DGLL_API int dgll_hip_gat_bwd_cols_strided(void* stream, const dgll_csr_plan* t_
     return gat_bwd_cols_impl(stream, t_plan, t_rowptr, t_col, nullptr, dn_scratch, ldn, H, ldh, T_rows, sd_scratch,
                              sd_scratch + heads, sd_stride, nullptr, nullptr, grad_H, ldgh, grad_T, dtype, n_cols, heads, fo,
                              alpha, 0, workspace, workspace_bytes, attn1, attn2, grad_S_rows);
+}
+
+// ---- the strided / row-score passes with attention dropout drawn in the kernels (gat_dropout.hpp) ---------------------------
+// T (with t_stride) XOR attn2 selects the form of the forward and of the rows pass, as the _strided / _rowscore entry points do.
+DGLL_API int dgll_hip_gat_fwd_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
+                                      const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* attn2,
+                                      void* out, int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int64_t n_cols, int heads,
+                                      int fo, float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
+                                      const uint32_t* seed) {
+    DGLL_REQUIRE((T != nullptr) != (attn2 != nullptr), "give T (with t_stride) or attn2, not both");
+    DGLL_REQUIRE(attn2 || t_stride >= heads, "t_stride must be at least heads");
+    DGLL_REQUIRE(n_cols > 0 && n_cols < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
+    if (attn2 && !rowscore_addressable(n_cols, ldh, dtype)) {
+        set_error("dgll_hip_gat_fwd_dropout: the row-score form needs H of at most 2^24 rows and 4 GB (pass T instead of attn2)");
+        return DGLL_ERR_UNSUPPORTED;
+    }
+    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, T, attn2 ? 0 : t_stride, nullptr, out, ldo, dtype, rowsum, nullptr, n_rows,
+                        heads, fo, alpha, apply_elu, 0, workspace, workspace_bytes, 0, 0, attn2, true, p, seed);
+}
+
+DGLL_API int dgll_hip_gat_bwd_rows_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
+                                           const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
+                                           const float* attn2, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
+                                           int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
+                                           int sd_stride, float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo,
+                                           float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
+                                           const uint32_t* seed) {
+    DGLL_REQUIRE((T != nullptr) != (attn2 != nullptr), "give T (with t_stride) or attn2, not both");
+    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && (attn2 || t_stride >= heads), "bad strided score arguments");
+    DGLL_REQUIRE(n_cols > 0 && n_cols < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
+    if (attn2 && !rowscore_addressable(n_cols, ldh, dtype)) {
+        set_error("dgll_hip_gat_bwd_rows_dropout: the row-score form needs H of at most 2^24 rows and 4 GB (pass T instead of attn2)");
+        return DGLL_ERR_UNSUPPORTED;
+    }
+    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, T, attn2 ? 0 : t_stride, nullptr, out, ldo, grad_out, ldg, dtype,
+                             rowsum, nullptr, dn_scratch, ldn, nullptr, sd_scratch, sd_stride, grad_S, n_rows, heads, fo, alpha,
+                             apply_elu, 0, 3, workspace, workspace_bytes, nullptr, attn2, true, p, seed);
+}
+
+DGLL_API int dgll_hip_gat_bwd_cols_dropout(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
+                                           const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
+                                           int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
+                                           void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
+                                           int fo, float alpha, void* workspace, size_t workspace_bytes,
+                                           const float* attn1, const float* attn2, const float* grad_S_rows, double p,
+                                           const uint32_t* seed) {
+    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && T_rows, "bad strided score arguments");
+    return gat_bwd_cols_impl(stream, t_plan, t_rowptr, t_col, nullptr, dn_scratch, ldn, H, ldh, T_rows, sd_scratch,
+                             sd_scratch + heads, sd_stride, nullptr, nullptr, grad_H, ldgh, grad_T, dtype, n_cols, heads, fo,
+                             alpha, 0, workspace, workspace_bytes, attn1, attn2, grad_S_rows, true, p, seed);
+}
+
+// The [nnz, heads] multipliers of a CSR as a tensor, from the one function the passes evaluate (tests; callers that want the mask).
+__global__ __launch_bounds__(kBlock) void gat_dropout_mask_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                  int64_t n_rows, int heads, const uint32_t* __restrict__ seed,
+                                                                  GatDropout d, float* __restrict__ out) {
+    const int64_t row = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const uint32_t s0 = seed[0], s1 = seed[1];
+    const uint32_t rk = gat_dropout_row_key(s0, s1, (uint32_t)row);
+    const int64_t b = rowptr[row], e = rowptr[row + 1];
+    for (int64_t k = b + lane_id(); k < e; k += kWave) {
+        const uint32_t ck = gat_dropout_col_key(s0, s1, (uint32_t)col[k]);
+        for (int h = 0; h < heads; ++h) out[k * heads + h] = gat_dropout_keep(gat_dropout_draw(rk, ck, (uint32_t)h), d);
+    }
+}
+
+static int gat_mask_args(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads, const uint32_t* seed, double p, float* out) {
+    DGLL_REQUIRE(rowptr && col && seed && out, "NULL argument");
+    DGLL_REQUIRE(heads > 0 && n_rows < ((int64_t)1 << 31), "heads must be positive, node ids 32-bit");
+    if (!(p >= 0.0 && p < 1.0)) {
+        set_error("attention dropout: p must lie in [0, 1)");
+        return DGLL_ERR_INVALID;
+    }
+    return DGLL_OK;
+}
+
+DGLL_API int dgll_hip_gat_dropout_mask(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads,
+                                       const uint32_t* seed, double p, float* out) {
+    if (n_rows <= 0) return DGLL_OK;
+    const int rc = gat_mask_args(rowptr, col, n_rows, heads, seed, p, out);
+    if (rc != DGLL_OK) return rc;
+    hipLaunchKernelGGL(gat_dropout_mask_kernel, dim3((uint32_t)((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), rowptr, col, n_rows, heads, seed, gat_dropout_params(p), out);
+    DGLL_HIP_TRY(hipGetLastError());
+    return DGLL_OK;
+}
+
+// the same on the host (all pointers host memory): a plain loop over the same function, no GPU needed
+DGLL_API int dgll_host_gat_dropout_mask(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads, const uint32_t* seed,
+                                        double p, float* out) {
+    if (n_rows <= 0) return DGLL_OK;
+    const int rc = gat_mask_args(rowptr, col, n_rows, heads, seed, p, out);
+    if (rc != DGLL_OK) return rc;
+    const GatDropout d = gat_dropout_params(p);
+    for (int64_t i = 0; i < n_rows; ++i)
+        for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+            for (int h = 0; h < heads; ++h)
+                out[k * heads + h] = gat_dropout_multiplier(seed[0], seed[1], (uint32_t)i, (uint32_t)col[k], (uint32_t)h, d);
+    return DGLL_OK;
 }
 
 DGLL_API int dgll_hip_gat_bwd_strided(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,

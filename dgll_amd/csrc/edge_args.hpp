@@ -1,6 +1,7 @@
 // edge_args.hpp -- launch arguments and wave-level helpers shared by the per-edge kernels (edge.hip, gat.hip).
 #pragma once
 #include "common.hpp"
+#include "gat_dropout.hpp"
 
 namespace dgll {
 
@@ -55,6 +56,11 @@ struct EdgeArgs {
     const float* attn1;         // fp32 [heads * fo]: a1 of every head, laid out like a row of H
     const float* attn2;         // fp32 [heads * fo]
     const float* gs_rows;       // fp32 [n_rows of this pass, heads]: grad_S of the pass's rows (from the rows pass)
+    // in-kernel attention dropout (gat_dropout.hpp; the DROP instantiations of gat2_kernel only).  The seed is READ by the kernel: a
+    // captured graph whose seed words are rewritten between replays draws a fresh mask on every replay.
+    float drop_p;               // probability of dropping an edge's attention weight, [0, 1)
+    GatDropout drop;            // its threshold and 1 / (1 - p), formed once on the host
+    const uint32_t* drop_seed;  // device pointer to the two 32-bit seed words
 };
 
 // Row epilogue of the exact rows pass for one (row, head): the launch's sums (sa, sb, sw) = (sum c.dot, sum c, sum w.dot) -- plus the
@@ -156,5 +162,12 @@ bool gat2_launch_1(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const E
 bool gat2_launch_3(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);   // pass 1, exact-dd form alone
 bool gat2_launch_3r(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);            // pass 1 exact, scores from the gathered rows
 bool gat2_launch_2(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);
+// gat_fwd_drop.hip / gat_fwd_rowscore_drop.hip / gat_bwd_rows_drop.hip / gat_bwd_rows_rowscore_drop.hip / gat_bwd_cols_drop.hip: the
+// same passes with the attention-dropout mask drawn in the kernel (a.drop, a.drop_seed); rows pass: the exact-dd form only
+bool gat2_launch_0d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
+bool gat2_launch_0rd(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
+bool gat2_launch_3d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
+bool gat2_launch_3rd(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
+bool gat2_launch_2d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
 
 }  // namespace dgll

@@ -5,8 +5,8 @@
 //   sparseGatConv.forward  gatconv.py:111-148   e_ij = exp(-leakyrelu(a1.h_i + a2.h_j)); out_i = sum_j e_ij h_j / sum_j e_ij; elu
 //   SpecialSpmmFunction    gatconv.py:60-81     the two backward products (here: two more gather passes, nothing per edge stored)
 //   SpGAT                  gatconv.py:174-199   `nheads` independent heads -- all of them in ONE launch here
-// (the max-subtracted softmax of the dense-adjacency gatConv, gatconv.py:30-54, and attention dropout stay on edge.hip's
-// first-generation kernels.)
+// (the max-subtracted softmax of the dense-adjacency gatConv, gatconv.py:30-54, stays on edge.hip's first-generation kernels, and so
+// does attention dropout given as an explicit [nnz, heads] multiplier array; dropout drawn IN the passes is the DROP form below.)
 //
 // Where the time of these passes goes (MI355X, 8 heads x 32 bf16, products-sized graph; tools/gat_ab.py): like the SpMM they are
 // bound by cache-line fills per edge -- 4 lines for the 512-byte feature row, plus ONE line for every separate per-node array
@@ -100,13 +100,23 @@ __device__ __forceinline__ float head_sum_dpp(float v) {
 // for v_dot2), takes the partial dot product with the row it has just gathered and sums over the head's lanes on the DPP path; each
 // lane then evaluates w_ij itself.  No score row is fetched (the FIFTH cache line per edge of the 8 x 32 bf16 layer), no
 // record phase, no LDS hand-over -- for 4 x more exponentials per edge, on a VALU that was a third busy.
-template <typename XT, typename YT, int EPV, int LPR, int NH, int U, int KIND, bool INROW = false, bool TROW = false>
+// DROP (forward, exact rows pass, transposed pass; not the in-row form): attention dropout, gatconv.py:132 -- the multiplier m_ij of
+// edge (i, j) and head k is a pure function of (seed, i, j, k) (gat_dropout.hpp) that every pass evaluates for itself, so no mask is
+// stored, as no w_ij is.  The denominator keeps every edge:  acc += m w h_j, den += w;  rows pass  sw += m w dot, sa += f m w dot,
+// sb += f w  (dd_i = -sw / den_i and ds_i = sa + dd_i sb keep their form and stay bilinear in the partial sums);  transposed pass
+// grad_H_j += m w DN_i, dt_j = sum_i c (m dot + dd_i) with the two ids swapped back for the draw.  The key half of the wave-uniform id
+// is formed once per row; in the record phase the edge's lane makes the draws of its heads and the record carries m w next to w (the
+// transposed pass's record {w, c} simply becomes {m w, m c}); in the row-score form the quad's lane that evaluates an edge's exponential
+// also makes its draw and hands m w round with w.  A template parameter: the instantiations without it are the code they were.
+template <typename XT, typename YT, int EPV, int LPR, int NH, int U, int KIND, bool INROW = false, bool TROW = false, bool DROP = false>
 // (the narrow in-row rows pass is held at 6 wavefronts per SIMD: the exact dd_i's extra sum took it from 79 to 86 VGPRs and from 6 to
 // 5 wavefronts, 2.56 -> 2.88 ms; bounded it fits 77 registers without scratch.  The 8-head form needs 12 bytes of scratch at that bound
 // and measured no faster: it runs at 83 registers / 5 wavefronts, 6.02 -> 6.17 ms for the exactness.)
 __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeof(XT) == 2) ? 6 : 1) void gat2_kernel(const EdgeArgs a) {
     typedef VecIO<XT, EPV> IO;
-    typedef typename std::conditional<KIND == 2, float2, float>::type rec_t;   // KIND 2: {w_ij, c_ij}, plus dd_i * c_ij in rec1;
+    static_assert(!DROP || (!INROW && KIND != 1), "in-kernel dropout: forward, exact rows pass and transposed pass, scores not in the rows' padding");
+    constexpr bool REC2 = KIND == 2 || (DROP && !TROW);             // DROP, record phase: {w_ij (signed in the rows pass), m_ij w_ij}
+    typedef typename std::conditional<REC2, float2, float>::type rec_t;        // KIND 2: {w_ij, c_ij}, plus dd_i * c_ij in rec1;
                                                                                // KIND 1: w_ij with the sign of z_ij (c_ij = w_ij * f, f = sign or sign * alpha)
     constexpr int SLOTS = kWave / LPR;
     constexpr bool ROWS = KIND == 1 || KIND == 3;                   // the rows pass: KIND 3 = its exact-dd form ALONE (no code of the
@@ -161,6 +171,8 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
             for (int q = 0; q < 4; ++q) a2p[q] = pack_bf16x2(a2f[2 * q], a2f[2 * q + 1]);
         }
     }
+    uint32_t sd0 = 0u, sd1 = 0u;                                   // DROP: the seed words, read here -- not launch arguments
+    if constexpr (DROP) { sd0 = a.drop_seed[0]; sd1 = a.drop_seed[1]; }
     WorkItem it = resolve_item(a, wave, 0);
     int col_first = 0;                                             // the item's first index batch (lane = edge), prefetched
     if (it.valid && it.b + lane < it.e) col_first = __builtin_nontemporal_load(a.col + it.b + lane);
@@ -186,6 +198,9 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
     float su[NH];
     load_heads_uniform<NH>(a.S, row, a.heads, h0, su);
     const float s_mine = s_first;                                  // TROW: s_i of this lane's own head
+    // DROP: the key half of this pass's own row -- the destination i, or in the transposed pass the source j
+    uint32_t own_key = 0u;
+    if constexpr (DROP) own_key = KIND == 2 ? gat_dropout_col_key(sd0, sd1, (uint32_t)row) : gat_dropout_row_key(sd0, sd1, (uint32_t)row);
 
     // ---- per-row prologue of the backward passes
     float dn[EPV];                     // KIND 1: DN_i (this lane's columns)
@@ -267,15 +282,25 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
             float tv[NH], dv[NH];
             load_heads<NH>(a.T, col_cur, a.tstride, a.heads, h0, tv);        // idle lanes hold column 0: a valid row
             if constexpr (KIND == 2) load_heads<NH>(a.DD, col_cur, a.tstride, a.heads, h0, dv);
+            uint32_t far_key = 0u;                                  // DROP: the key half of the edge's other end
+            if constexpr (DROP) far_key = KIND == 2 ? gat_dropout_row_key(sd0, sd1, (uint32_t)col_cur) : gat_dropout_col_key(sd0, sd1, (uint32_t)col_cur);
 #pragma unroll
             for (int k = 0; k < NH; ++k) {
                 const float z = su[k] + tv[k];
                 float w = __expf(a.sign * lrelu(z, a.alpha));
                 w = (live && h0 + k < a.heads) ? w : 0.0f;
                 const float cc = w * a.sign * (z > 0.0f ? 1.0f : a.alpha);
-                if constexpr (KIND == 0) rec[k * kRecStride + lane] = w;
-                if constexpr (ROWS) rec[k * kRecStride + lane] = z > 0.0f ? w : -w;
-                if constexpr (KIND == 2) { rec[k * kRecStride + lane] = make_float2(w, cc); rec1[k * kRecStride + lane] = dv[k] * cc; }
+                if constexpr (DROP) {
+                    const uint32_t draw = KIND == 2 ? gat_dropout_draw(far_key, own_key, (uint32_t)(h0 + k)) : gat_dropout_draw(own_key, far_key, (uint32_t)(h0 + k));
+                    const float m = gat_dropout_keep(draw, a.drop);
+                    if constexpr (KIND == 0) rec[k * kRecStride + lane] = make_float2(w, m * w);
+                    if constexpr (ROWS) rec[k * kRecStride + lane] = make_float2(z > 0.0f ? w : -w, m * w);
+                    if constexpr (KIND == 2) { rec[k * kRecStride + lane] = make_float2(m * w, m * cc); rec1[k * kRecStride + lane] = dv[k] * cc; }
+                } else {
+                    if constexpr (KIND == 0) rec[k * kRecStride + lane] = w;
+                    if constexpr (ROWS) rec[k * kRecStride + lane] = z > 0.0f ? w : -w;
+                    if constexpr (KIND == 2) { rec[k * kRecStride + lane] = make_float2(w, cc); rec1[k * kRecStride + lane] = dv[k] * cc; }
+                }
             }
         }
         // idle lanes of the last batch repeat its last valid column (same cache lines as a live request; their records are zero)
@@ -288,10 +313,13 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
             typename IO::raw_t v[U];
             rec_t rr[U];
             float r1[U];
+            float mw[U];                                            // DROP, row-score form: m_ij w_ij
+            int cjs[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int idx = j + u * SLOTS + slot;
                 const int cj = __shfl(gcol, idx);
+                cjs[u] = cj;
                 if constexpr (TROW) {
                     // 32-bit byte offset from the uniform base: one full-rate v_mad_u32_u24 and the load's scalar-base form instead of
                     // v_mad_u64_u32 + a 64-bit add per gather (forward 5.08 -> 4.95 ms; the entry point admits matrices under 4 GB and
@@ -341,6 +369,11 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
                             if constexpr (KIND == 0) rr[u] = w4[u];
                             if constexpr (ROWS) rr[u] = z[u] > 0.0f ? w4[u] : -w4[u];
                         }
+                        if constexpr (DROP) {   // the draw like the exponential: lane hs makes edge hs's and hands m w round the quad
+                            const int cs = hs == 0 ? cjs[0] : (hs == 1 ? cjs[1] : (hs == 2 ? cjs[2] : cjs[3]));
+                            const float ms = ws * gat_dropout_keep(gat_dropout_draw(own_key, gat_dropout_col_key(sd0, sd1, (uint32_t)cs), (uint32_t)(h0 + hk)), a.drop);
+                            mw[0] = dpp_take<0x00>(ms); mw[1] = dpp_take<0x55>(ms); mw[2] = dpp_take<0xAA>(ms); mw[3] = dpp_take<0xFF>(ms);
+                        }
                     } else {
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
@@ -348,6 +381,8 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
                             if constexpr (decltype(masked)::value) w = (j + u * SLOTS + slot < nb) ? w : 0.0f;
                             if constexpr (KIND == 0) rr[u] = w;
                             if constexpr (ROWS) rr[u] = z[u] > 0.0f ? w : -w;
+                            if constexpr (DROP)
+                                mw[u] = w * gat_dropout_keep(gat_dropout_draw(own_key, gat_dropout_col_key(sd0, sd1, (uint32_t)cjs[u]), (uint32_t)(h0 + hk)), a.drop);
                         }
                     }
                 };
@@ -388,7 +423,15 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (KIND == 0) {
+                if constexpr (KIND == 0 && DROP) {
+                    float wu, mu;                                   // the denominator keeps the dropped edges
+                    if constexpr (TROW) { wu = rr[u]; mu = mw[u]; } else { wu = rr[u].x; mu = rr[u].y; }
+                    sb += wu;
+                    float f[EPV];
+                    IO::unpack(v[u], f);
+#pragma unroll
+                    for (int i = 0; i < EPV; ++i) acc[i] = fmaf(mu, f[i], acc[i]);
+                } else if constexpr (KIND == 0) {
                     sb += rr[u];
                     float f[EPV];
                     IO::unpack(v[u], f);
@@ -411,9 +454,13 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
                         }
                         if constexpr (INROW) dot = col_ok ? dot : 0.0f;   // the score lane holds score bits, not features: 0 x NaN
                         // one record per (edge, head): |r| = w_ij, its sign = the sign of z_ij; c_ij = w_ij * f
-                        const float wv = fabsf(rr[u]);
-                        const float fz = rr[u] > 0.0f ? a.sign : a.sign * a.alpha;
-                        const float dw = dot * wv;
+                        float wsg, wm;                              // signed w_ij; what multiplies the dot product: m_ij w_ij under DROP
+                        if constexpr (DROP && TROW) { wsg = rr[u]; wm = mw[u]; }
+                        else if constexpr (DROP) { wsg = rr[u].x; wm = rr[u].y; }
+                        else { wsg = rr[u]; wm = fabsf(wsg); }
+                        const float wv = fabsf(wsg);
+                        const float fz = wsg > 0.0f ? a.sign : a.sign * a.alpha;
+                        const float dw = dot * wm;
                         sw += dw;
                         sa = fmaf(fz, dw, sa);
                         sb = fmaf(fz, wv, sb);
@@ -529,12 +576,12 @@ __global__ __launch_bounds__(kBlock, ((KIND == 1 || KIND == 3) && INROW && sizeo
 }
 
 // ---- dispatch: (lanes per row, heads per wavefront) pairs with 1 <= LPR / NH ------------------------------------------------
-template <typename XT, typename YT, int EPV, int LPR, int KIND, bool TROW = false>
+template <typename XT, typename YT, int EPV, int LPR, int KIND, bool TROW = false, bool DROP = false>
 static bool gat2_launch_nh(const EdgeArgs& a, int nh, dim3 grid, hipStream_t s, bool inrow) {
-#define DGLL_GAT2(NHV) hipLaunchKernelGGL((gat2_kernel<XT, YT, EPV, LPR, NHV, 4, KIND, false, TROW>), grid, dim3(kBlock), 0, s, a); return true
+#define DGLL_GAT2(NHV) hipLaunchKernelGGL((gat2_kernel<XT, YT, EPV, LPR, NHV, 4, KIND, false, TROW, DROP>), grid, dim3(kBlock), 0, s, a); return true
     switch (nh) {
         case 1:
-            if constexpr (!TROW) {
+            if constexpr (!TROW && !DROP) {
                 if (inrow) { hipLaunchKernelGGL((gat2_kernel<XT, YT, EPV, LPR, 1, 4, KIND, true>), grid, dim3(kBlock), 0, s, a); return true; }
             }
             DGLL_GAT2(1);
@@ -546,22 +593,22 @@ static bool gat2_launch_nh(const EdgeArgs& a, int nh, dim3 grid, hipStream_t s, 
 #undef DGLL_GAT2
 }
 
-template <typename XT, typename YT, int EPV, int KIND, bool TROW = false>
+template <typename XT, typename YT, int EPV, int KIND, bool TROW = false, bool DROP = false>
 static bool gat2_launch_lpr(const EdgeArgs& a, int lpr, int nh, dim3 grid, hipStream_t s, bool inrow) {
     switch (lpr) {
-        case 4: return gat2_launch_nh<XT, YT, EPV, 4, KIND, TROW>(a, nh, grid, s, inrow);
-        case 8: return gat2_launch_nh<XT, YT, EPV, 8, KIND, TROW>(a, nh, grid, s, inrow);
-        case 16: return gat2_launch_nh<XT, YT, EPV, 16, KIND, TROW>(a, nh, grid, s, inrow);
-        case 32: return gat2_launch_nh<XT, YT, EPV, 32, KIND, TROW>(a, nh, grid, s, inrow);
-        case 64: return gat2_launch_nh<XT, YT, EPV, 64, KIND, TROW>(a, nh, grid, s, inrow);
+        case 4: return gat2_launch_nh<XT, YT, EPV, 4, KIND, TROW, DROP>(a, nh, grid, s, inrow);
+        case 8: return gat2_launch_nh<XT, YT, EPV, 8, KIND, TROW, DROP>(a, nh, grid, s, inrow);
+        case 16: return gat2_launch_nh<XT, YT, EPV, 16, KIND, TROW, DROP>(a, nh, grid, s, inrow);
+        case 32: return gat2_launch_nh<XT, YT, EPV, 32, KIND, TROW, DROP>(a, nh, grid, s, inrow);
+        case 64: return gat2_launch_nh<XT, YT, EPV, 64, KIND, TROW, DROP>(a, nh, grid, s, inrow);
         default: return false;
     }
 }
 
-template <int KIND, bool TROW = false>
+template <int KIND, bool TROW = false, bool DROP = false>
 static bool gat2_launch_kind(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
-    if (dtype == DGLL_F32) return gat2_launch_lpr<float, float, 4, KIND, TROW>(a, lpr, nh, grid, s, inrow);
-    return gat2_launch_lpr<bf16_t, bf16_t, 8, KIND, TROW>(a, lpr, nh, grid, s, inrow);
+    if (dtype == DGLL_F32) return gat2_launch_lpr<float, float, 4, KIND, TROW, DROP>(a, lpr, nh, grid, s, inrow);
+    return gat2_launch_lpr<bf16_t, bf16_t, 8, KIND, TROW, DROP>(a, lpr, nh, grid, s, inrow);
 }
 
 }  // namespace dgll

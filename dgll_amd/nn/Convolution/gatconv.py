@@ -7,6 +7,10 @@ Interface mirror of /root/reference/dgll/nn/Convolution/gatconv.py:
   GAT / SpGAT(nfeat, nhid, nclass, dropout, alpha, nheads)                 8-head models         gatconv.py:154-199
 with identical parameter names (`W`, `a`, `attention_%d`, `out_att`) and initialisers.
 
+Attention dropout of sparseGatConv / SpGAT in training (gatconv.py:132) is drawn inside the gather kernels from a seed taken from
+torch's device generator -- no [nnz, heads] mask tensor; DGLL_GAT_DROPOUT=mask restores the materialised F.dropout mask on the
+first-generation kernels (gatConv / GAT always use that form).
+
 On the GPU each layer is ONE fused kernel (dgll_hip_gat_fwd): edge scores are formed from two per-node dot
 products s_i = a[:fo].h_i, t_j = a[fo:].h_j instead of the reference's materialised [2*fo, E] edge_h
 (gatconv.py:122), all heads of SpGAT/GAT run in the same launch (the reference calls heads one by one,
@@ -151,19 +155,29 @@ def pack_heads(Ws, a1s, a2s, fo_pad):
 
 
 def _attention_dropout(graph, heads, p, training, device):
-    """Per-edge, per-head multipliers of F.dropout on the attention weights (gatconv.py:37,132)."""
+    """Per-edge, per-head multipliers of F.dropout on the attention weights (gatconv.py:37,132) as an [nnz, heads] tensor: the form
+    gatConv (mode 1) uses, and sparseGatConv with DGLL_GAT_DROPOUT=mask or p = 1."""
     if not training or p <= 0.0:
         return None
     return F.dropout(F.ones(graph.nnz, heads, device=device), p, training=True)
+
+
+def _dropout_in_kernel(mode, p, training):
+    """sparseGatConv's attention dropout is drawn inside the gather kernels (ops.gat_layer's dropout_p: no per-edge tensor, forward
+    or backward) unless DGLL_GAT_DROPOUT=mask asks for the materialised mask.  Read per call: tests switch it."""
+    return mode == 0 and training and 0.0 < p < 1.0 and os.environ.get("DGLL_GAT_DROPOUT", "kernel") != "mask"
 
 
 def _fused_heads(x, adj, Ws, a1s, a2s, alpha, concat, mode, dropout, training):
     """Shared GPU path: Ws [heads][Fin, fo], a1s/a2s [heads][fo] -> [N, heads*fo]."""
     heads, fo = len(Ws), Ws[0].shape[1]
     graph = as_csr_graph(adj)
-    edge_scale = _attention_dropout(graph, heads, dropout, training, x.device)
-    # sparseGatConv's form without attention dropout runs on the second-generation kernels: any per-head width that is a
-    # whole number of 16-byte vectors; the max-subtracted / dropout forms need a power of two of them
+    in_kernel = _dropout_in_kernel(mode, dropout, training)
+    edge_scale = None if in_kernel else _attention_dropout(graph, heads, dropout, training, x.device)
+    drop_p = float(dropout) if in_kernel else 0.0
+    drop_seed = ops.dropout_seed(x.device) if in_kernel else None     # torch's generator on the device: torch.manual_seed, capture-safe
+    # sparseGatConv's form (attention dropout, if any, drawn in the kernels) runs on the second-generation kernels: any per-head
+    # width that is a whole number of 16-byte vectors; the max-subtracted / materialised-mask forms need a power of two of them
     strided = mode == 0 and edge_scale is None
     fo_pad = ops.head_width_padded(fo, x.dtype, pow2=not strided)
     # The per-head padding is applied to the WEIGHTS (a [Fin, heads*fo_pad] matrix with zero columns), not to the activations:
@@ -177,12 +191,12 @@ def _fused_heads(x, adj, Ws, a1s, a2s, alpha, concat, mode, dropout, training):
         # scores + aggregation as ONE autograd node (ops.gat_layer): the scores' own gradient w.r.t. h rides in the epilogue of
         # the transposed gather pass.  h is this function's own temporary (dense.linear allocates narrow rows on 128-byte
         # lines): its row padding may carry the per-node scores the gather passes fetch per edge
-        out = ops.gat_layer(graph, h, A, heads, alpha, apply_elu=concat, pack_scores=True)
+        out = ops.gat_layer(graph, h, A, heads, alpha, apply_elu=concat, pack_scores=True, dropout_p=drop_p, dropout_seed=drop_seed)
     else:
         st = dense.skinny_linear(h, A)                                         # fp32 [N, 2*heads]
         s, t = st[:, :heads], st[:, heads:]
         out = ops.gat_aggregate(graph, h, s, t, heads, alpha, apply_elu=concat, mode=mode, edge_scale=edge_scale,
-                                pack_scores=strided)
+                                pack_scores=strided, dropout_p=drop_p, dropout_seed=drop_seed)
     empty = _edgeless_rows(graph)
     if empty is not None:
         if mode == 1:

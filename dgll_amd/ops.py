@@ -504,4 +504,5 @@ def cross_entropy(logits, labels, reduction="mean", fold_relu=False):
     return _CrossEntropy.apply(logits, labels, reduction, token)
 
 
-from .ops_edge import gat_aggregate, gat_layer, head_width_padded, sddmm_raw, segment_max  # noqa: E402,F401
+from .ops_edge import (dropout_seed, gat_aggregate, gat_dropout_mask, gat_layer, head_width_padded, sddmm_raw,  # noqa: E402,F401
+                       segment_max)

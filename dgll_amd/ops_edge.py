@@ -118,7 +118,8 @@ def segment_max(graph, x):
 # ------------------------------------------------------------------------------------------------ fused GAT
 def head_width_padded(fo, dtype, pow2=True):
     """Per-head column count the kernels need: a whole number of 16-byte vectors -- a power of two of them for the
-    first-generation kernels (max-subtracted softmax, attention dropout), any number for sparseGatConv's form."""
+    first-generation kernels (max-subtracted softmax, attention dropout given as an edge_scale array), any number for
+    sparseGatConv's form, with or without dropout drawn in the kernels."""
     epv = _epv(dtype)
     vecs = -(-fo // epv)
     if not pow2:
@@ -150,18 +151,60 @@ ROW_SCORES = os.environ.get("DGLL_GAT_ROW_SCORES", "1") != "0"     # 0: the forw
 ROW_SCORES_BWD = os.environ.get("DGLL_GAT_ROW_SCORES_BWD", "1") != "0"   # the rows pass of the backward in the same form (6.07 -> 5.68 ms)
 
 
-def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, attn2=None):
+def dropout_seed(device):
+    """Two 32-bit seed words on `device` from torch's generator there (follows torch.manual_seed; safe under graph capture: a replay
+    draws new words, and the kernels read them from this tensor)."""
+    return torch.randint(-2 ** 31, 2 ** 31 - 1, (2,), dtype=torch.int32, device=device)
+
+
+def _check_dropout(p, seed, device):
+    """(p, seed) of an active in-kernel dropout, or None."""
+    p = float(p)
+    if p == 0.0:
+        return None
+    if not 0.0 < p < 1.0:
+        raise ValueError("dropout_p must lie in [0, 1), got %r" % p)
+    if seed is None:
+        seed = dropout_seed(device)
+    if seed.dtype != torch.int32 or seed.numel() != 2 or seed.device != device or not seed.is_contiguous():
+        raise ValueError("dropout_seed must be a contiguous 2-element int32 tensor on the layer's device")
+    return p, seed
+
+
+def gat_dropout_mask(graph, heads, p, seed):
+    """fp32 [nnz, heads] multipliers the kernels draw for (p, seed) -- dgll_hip_gat_dropout_mask for a graph on the GPU (seed: 2-element
+    int32 tensor there), dgll_host_gat_dropout_mask for host tensors.  For tests and for the explicit edge_scale= path; training with
+    dropout_p never materialises it."""
+    dev = graph.rowptr.device
+    seed = seed.to(torch.int32).contiguous()
+    out = torch.empty((graph.nnz, heads), dtype=torch.float32, device=dev)
+    col = graph.col.contiguous()
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            code = _lib.lib.dgll_hip_gat_dropout_mask(_stream(dev), graph.rowptr.data_ptr(), col.data_ptr(), graph.n_rows, heads,
+                                                      seed.data_ptr(), float(p), out.data_ptr())
+        _lib.check(code, "dgll_hip_gat_dropout_mask")
+    else:
+        code = _lib.lib.dgll_host_gat_dropout_mask(graph.rowptr.data_ptr(), col.data_ptr(), graph.n_rows, heads, seed.data_ptr(), float(p),
+                                                   out.data_ptr())
+        _lib.check(code, "dgll_host_gat_dropout_mask")
+    return out
+
+
+def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, attn2=None, dropout=None):
     """Forward gather pass on dgll_hip_gat_fwd_strided.  Returns (h with aligned rows, s, t, out, rowsum, packed).
     attn2: fp32 [heads * fo], a2 of every head laid out like a row of h (t = h . a2 per head): when the scores cannot ride in the rows'
     padding the pass forms t_j from the row it gathers anyway instead of fetching T[j] (dgll_hip_gat_fwd_rowscore; the reference builds
-    its logit from the gathered rows too, gatconv.py:122-125)."""
+    its logit from the gathered rows too, gatconv.py:122-125).
+    dropout: (p, seed) -- attention dropout drawn in the kernel (dgll_hip_gat_fwd_dropout, either score form; the scores do not ride in
+    the rows' padding then: the in-row form has no dropout instantiation)."""
     _require_cuda(h, s, t, graph.rowptr)
     dev = h.device
     h = _ready(h)
     esz, width = h.element_size(), heads * fo
     s = s.to(torch.float32).contiguous()
     t = t.to(torch.float32).contiguous()
-    packed = bool(pack_scores) and (h.stride(0) - width) * esz >= 4 * heads
+    packed = bool(pack_scores) and dropout is None and (h.stride(0) - width) * esz >= 4 * heads
     if packed:
         t_gather = _row_slot(h, width * esz, heads)
         t_gather.copy_(t)
@@ -176,9 +219,20 @@ def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_score
     # (the row-score kernel addresses h by 32-bit byte offsets: at most 2^24 rows and 4 GB)
     row_scores = attn2 is not None and not packed and ROW_SCORES and h.shape[0] <= (1 << 24) and h.stride(0) * esz < (1 << 24) \
         and h.shape[0] * h.stride(0) * esz <= 0xFFFFFFFF
-    end = timer.start(("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, "packed" if packed else ("rowscore" if row_scores else "")), dev) if timer else None
+    form = "packed" if packed else ("rowscore" if row_scores else "")
+    if dropout is not None:
+        form = (form + " dropout").strip()
+    end = timer.start(("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, form), dev) if timer else None
     with torch.cuda.device(dev):
-        if row_scores:
+        if dropout is not None:
+            a2 = attn2.detach().to(torch.float32).contiguous() if row_scores else None
+            code = _lib.lib.dgll_hip_gat_fwd_dropout(
+                _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
+                None if row_scores else t_gather.data_ptr(), 0 if row_scores else t_gather.stride(0),
+                a2.data_ptr() if row_scores else None, out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), graph.n_rows,
+                int(h.shape[0]), heads, fo, float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, ws_bytes,
+                dropout[0], dropout[1].data_ptr())
+        elif row_scores:
             a2 = attn2.detach().to(torch.float32).contiguous()
             code = _lib.lib.dgll_hip_gat_fwd_rowscore(
                 _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
@@ -191,13 +245,16 @@ def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_score
                 graph.n_rows, heads, fo, float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, ws_bytes)
     if end is not None:
         end.record(torch.cuda.current_stream(dev))
-    _lib.check(code, "dgll_hip_gat_fwd_rowscore" if row_scores else "dgll_hip_gat_fwd_strided")
+    _lib.check(code, "dgll_hip_gat_fwd_dropout" if dropout is not None else
+               ("dgll_hip_gat_fwd_rowscore" if row_scores else "dgll_hip_gat_fwd_strided"))
     return h, s, t, out, rowsum, packed
 
 
-def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, apply_elu, packed, attn=None, rows_first=False):
+def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, apply_elu, packed, attn=None, rows_first=False,
+                          dropout=None):
     """Both backward gather passes (dgll_hip_gat_bwd_rows_strided, _cols_strided).  attn = (a1, a2) fp32 [heads * fo]: the
     scores are S = H.a1, T = H.a2 per head and their contribution to grad_h is added by the second pass's epilogue.
+    dropout: the forward's (p, seed): both passes draw the same mask again (dgll_hip_gat_bwd_rows_dropout, _cols_dropout).
     Returns (grad_h, grad_s, grad_t)."""
     dev, esz, width = h.device, h.element_size(), heads * fo
     g = _ready(g.to(h.dtype))
@@ -216,7 +273,7 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
                    int(_lib.lib.dgll_hip_gat_workspace_bytes(t_plan, heads, fo)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     timer = _launch_timer()
-    tag = (heads, fo, str(h.dtype), graph.nnz, "packed" if packed else "")
+    tag = (heads, fo, str(h.dtype), graph.nnz, "packed" if packed else ("dropout" if dropout is not None else ""))
     wsp = ws.data_ptr() if ws is not None else None
     a1 = a2 = None
     gs_cols = grad_s
@@ -232,8 +289,15 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
         st = _stream(dev)
         small = h.shape[0] <= (1 << 24) and h.stride(0) * esz < (1 << 24) and h.shape[0] * h.stride(0) * esz <= 0xFFFFFFFF
         rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and small
-        end = timer.start(("gat", "bwd_rows") + (tag[:4] + ("rowscore",) if rows_rowscore else tag), dev) if timer else None
-        if rows_rowscore:      # t_j from the gathered rows, as in the forward
+        end = timer.start(("gat", "bwd_rows") + (tag[:4] + (("rowscore " + tag[4]).strip(),) if rows_rowscore else tag), dev) if timer else None
+        if dropout is not None:
+            code = _lib.lib.dgll_hip_gat_bwd_rows_dropout(
+                st, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
+                None if rows_rowscore else t_gather.data_ptr(), 0 if rows_rowscore else t_gather.stride(0),
+                a2.data_ptr() if rows_rowscore else None, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h),
+                rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows,
+                int(h.shape[0]), heads, fo, alpha, apply_elu, wsp, ws_bytes, dropout[0], dropout[1].data_ptr())
+        elif rows_rowscore:      # t_j from the gathered rows, as in the forward
             code = _lib.lib.dgll_hip_gat_bwd_rows_rowscore(
                 st, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), a2.data_ptr(),
                 out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h), rowsum.data_ptr(), dn.data_ptr(), dn.stride(0),
@@ -246,41 +310,48 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
                 heads, fo, alpha, apply_elu, wsp, ws_bytes)
         if end is not None:
             end.record(torch.cuda.current_stream(dev))
-        _lib.check(code, "dgll_hip_gat_bwd_rows_rowscore" if rows_rowscore else "dgll_hip_gat_bwd_rows_strided")
+        _lib.check(code, "dgll_hip_gat_bwd_rows_dropout" if dropout is not None else
+                   ("dgll_hip_gat_bwd_rows_rowscore" if rows_rowscore else "dgll_hip_gat_bwd_rows_strided"))
         if gs_cols is not grad_s:
             gs_cols[:graph.n_rows].copy_(grad_s)
         end = timer.start(("gat", "bwd_cols") + tag, dev) if timer else None
-        code = _lib.lib.dgll_hip_gat_bwd_cols_strided(
-            st, t_plan, gt.rowptr.data_ptr(), gt.col.data_ptr(), dn.data_ptr(), dn.stride(0), h.data_ptr(), h.stride(0),
-            t.data_ptr(), sd.data_ptr(), sd.stride(0), grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(h),
-            graph.n_cols, heads, fo, alpha, wsp, ws_bytes, a1.data_ptr() if a1 is not None else None,
-            a2.data_ptr() if a2 is not None else None, gs_cols.data_ptr() if a1 is not None else None)
+        cols_args = (st, t_plan, gt.rowptr.data_ptr(), gt.col.data_ptr(), dn.data_ptr(), dn.stride(0), h.data_ptr(), h.stride(0),
+                     t.data_ptr(), sd.data_ptr(), sd.stride(0), grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(h),
+                     graph.n_cols, heads, fo, alpha, wsp, ws_bytes, a1.data_ptr() if a1 is not None else None,
+                     a2.data_ptr() if a2 is not None else None, gs_cols.data_ptr() if a1 is not None else None)
+        if dropout is not None:
+            code = _lib.lib.dgll_hip_gat_bwd_cols_dropout(*cols_args, dropout[0], dropout[1].data_ptr())
+        else:
+            code = _lib.lib.dgll_hip_gat_bwd_cols_strided(*cols_args)
         if end is not None:
             end.record(torch.cuda.current_stream(dev))
-        _lib.check(code, "dgll_hip_gat_bwd_cols_strided")
+        _lib.check(code, "dgll_hip_gat_bwd_cols_dropout" if dropout is not None else "dgll_hip_gat_bwd_cols_strided")
     return grad_h, grad_s, grad_t
 
 
 class _GatAggregateStrided(torch.autograd.Function):
-    """sparseGatConv's form (exp(-leakyrelu), no attention dropout) on the second-generation kernels
-    (dgll_hip_gat_fwd_strided / _bwd_*_strided).  These passes are bound by cache-line fills per edge, so per-node scalars
+    """sparseGatConv's form (exp(-leakyrelu); attention dropout drawn in the kernels from (dropout_p, dropout_seed) when given) on
+    the second-generation kernels (dgll_hip_gat_fwd_strided / _bwd_*_strided, or their *_dropout forms).  These passes are bound by cache-line fills per edge, so per-node scalars
     that are gathered per edge live next to what is gathered anyway: with `pack_scores` (the caller owns the padding behind
     h's rows) T sits in the padding of the feature rows -- a 47-class output row is 96 of 128 bytes -- and the backward keeps
     {s_i, dd_i} in the padding of its DN rows; without room they are compact / side-by-side arrays."""
 
     @staticmethod
-    def forward(ctx, h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores):
-        h, s, t, out, rowsum, packed = _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores)
+    def forward(ctx, h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, dropout_p=0.0, dropout_seed=None):
+        drop = _check_dropout(dropout_p, dropout_seed, h.device)
+        h, s, t, out, rowsum, packed = _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, dropout=drop)
         ctx.graph, ctx.cfg, ctx.packed = graph, (heads, fo, float(alpha), int(apply_elu)), packed
-        ctx.save_for_backward(h, s, t, out, rowsum)
+        ctx.drop_p = drop[0] if drop else 0.0
+        ctx.save_for_backward(h, s, t, out, rowsum, drop[1] if drop else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        h, s, t, out, rowsum = ctx.saved_tensors
+        h, s, t, out, rowsum, seed = ctx.saved_tensors
         heads, fo, alpha, apply_elu = ctx.cfg
-        grad_h, grad_s, grad_t = _gat_strided_backward(g, h, s, t, out, rowsum, ctx.graph, heads, fo, alpha, apply_elu, ctx.packed)
-        return grad_h, grad_s, grad_t, None, None, None, None, None, None
+        grad_h, grad_s, grad_t = _gat_strided_backward(g, h, s, t, out, rowsum, ctx.graph, heads, fo, alpha, apply_elu, ctx.packed,
+                                                       dropout=(ctx.drop_p, seed) if seed is not None else None)
+        return grad_h, grad_s, grad_t, None, None, None, None, None, None, None, None
 
 
 class _GatLayerStrided(torch.autograd.Function):
@@ -290,10 +361,11 @@ class _GatLayerStrided(torch.autograd.Function):
     contribution to grad_H: the transposed gather pass adds grad_S * a1 + grad_T * a2 in its epilogue."""
 
     @staticmethod
-    def forward(ctx, h, A, graph, heads, fo, alpha, apply_elu, pack_scores):
+    def forward(ctx, h, A, graph, heads, fo, alpha, apply_elu, pack_scores, dropout_p=0.0, dropout_seed=None):
         """h: one row per COLUMN of `graph`; a rectangular graph's rows are its first n_rows columns (dist.py's merged adjacency)."""
         from . import dense
 
+        drop = _check_dropout(dropout_p, dropout_seed, h.device)
         h = _ready(h)
         if h.shape[0] != graph.n_cols or graph.n_rows > graph.n_cols:
             raise ValueError("gat_layer: h needs one row per column of the adjacency, whose rows are its first columns")
@@ -302,22 +374,24 @@ class _GatLayerStrided(torch.autograd.Function):
               else dense.mm_nt(h, Ad.t()).float())
         # a2 of every head laid out like a row of h (A is block-diagonal: column heads + k holds a2 of head k in rows k fo .. (k + 1) fo)
         h, s, t, out, rowsum, packed = _gat_strided_forward(h, st[:graph.n_rows, :heads], st[:, heads:], graph, heads, fo, alpha, apply_elu,
-                                                            pack_scores, attn2=Ad[:, heads:].float().sum(1))
+                                                            pack_scores, attn2=Ad[:, heads:].float().sum(1), dropout=drop)
         ctx.graph, ctx.cfg, ctx.packed = graph, (heads, fo, float(alpha), int(apply_elu)), packed
-        ctx.save_for_backward(h, Ad, s, t, out, rowsum)
+        ctx.drop_p = drop[0] if drop else 0.0
+        ctx.save_for_backward(h, Ad, s, t, out, rowsum, drop[1] if drop else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         from . import dense
 
-        h, Ad, s, t, out, rowsum = ctx.saved_tensors
+        h, Ad, s, t, out, rowsum, seed = ctx.saved_tensors
         heads, fo, alpha, apply_elu = ctx.cfg
         # block-diagonal A: column k holds a1 of head k in rows k fo .. (k + 1) fo, column heads + k holds a2
         a1 = Ad[:, :heads].float().sum(1)
         a2 = Ad[:, heads:].float().sum(1)
         grad_h, grad_s, grad_t = _gat_strided_backward(g, h, s, t, out, rowsum, ctx.graph, heads, fo, alpha, apply_elu, ctx.packed,
-                                                       attn=(a1, a2) if ctx.needs_input_grad[0] else None, rows_first=True)
+                                                       attn=(a1, a2) if ctx.needs_input_grad[0] else None, rows_first=True,
+                                                       dropout=(ctx.drop_p, seed) if seed is not None else None)
         grad_A = None
         if ctx.needs_input_grad[1]:      # dA = H^T . [grad_S | grad_T], columns padded to a 16-byte row for the split-K kernel
             n = 2 * heads
@@ -326,7 +400,7 @@ class _GatLayerStrided(torch.autograd.Function):
             gst[:grad_s.shape[0], :heads] = grad_s
             gst[:, heads:n] = grad_t
             grad_A = dense.grad_weight(h, gst)[:, :n]
-        return (grad_h if ctx.needs_input_grad[0] else None), grad_A, None, None, None, None, None, None
+        return (grad_h if ctx.needs_input_grad[0] else None), grad_A, None, None, None, None, None, None, None, None
 
 
 def _launch_timer():
@@ -394,10 +468,14 @@ class _GatAggregate(torch.autograd.Function):
         return grad_h, grad_s, grad_t, None, None, None, None, None, None, None
 
 
-def gat_aggregate(graph, h, s, t, heads, alpha, apply_elu=True, mode=0, edge_scale=None, pack_scores=False):
+def gat_aggregate(graph, h, s, t, heads, alpha, apply_elu=True, mode=0, edge_scale=None, pack_scores=False, dropout_p=0.0,
+                  dropout_seed=None):
     """Fused multi-head edge-softmax + aggregation.  h: [N, heads*fo] with fo already padded per `head_width_padded`
     (pow2=False suffices for mode 0 without edge_scale); s, t: [N, heads].  pack_scores: the caller owns the padding behind
-    h's rows (h.stride(0) > h.shape[1]) and lets the kernels keep per-node scores there."""
+    h's rows (h.stride(0) > h.shape[1]) and lets the kernels keep per-node scores there.
+    dropout_p in (0, 1) (mode 0 without edge_scale): attention dropout drawn inside the kernels, nothing stored per edge;
+    dropout_seed: 2-element int32 tensor on h's device (None: drawn from torch's generator there), kept for the backward.  The mask
+    is a function of (seed, row, column, head): duplicate (row, column) entries of an uncoalesced adjacency share a draw."""
     if not isinstance(graph, CSRGraph):
         raise TypeError("gat_aggregate expects a CSRGraph")
     fo = h.shape[1] // heads
@@ -406,19 +484,22 @@ def gat_aggregate(graph, h, s, t, heads, alpha, apply_elu=True, mode=0, edge_sca
         raise ValueError("per-head width %d is not padded for the kernels (need %d)"
                          % (fo, head_width_padded(fo, h.dtype, pow2=not strided)))
     if strided:
-        return _GatAggregateStrided.apply(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores)
+        return _GatAggregateStrided.apply(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, dropout_p, dropout_seed)
+    if float(dropout_p) != 0.0:
+        raise ValueError("dropout_p needs mode 0 without edge_scale (in-kernel dropout is sparseGatConv's form)")
     return _GatAggregate.apply(h, s, t, edge_scale, graph, heads, fo, alpha, apply_elu, mode)
 
 
-def gat_layer(graph, h, A, heads, alpha, apply_elu=True, pack_scores=False):
+def gat_layer(graph, h, A, heads, alpha, apply_elu=True, pack_scores=False, dropout_p=0.0, dropout_seed=None):
     """sparseGatConv after its transform as one autograd node: h [N, heads*fo] (per-head width a whole number of 16-byte
-    vectors), A [heads*fo, 2*heads] = blockdiag(a1_k | a2_k).  GPU, mode 0, no attention dropout."""
+    vectors), A [heads*fo, 2*heads] = blockdiag(a1_k | a2_k).  GPU, mode 0.  dropout_p / dropout_seed: attention dropout drawn
+    inside the kernels, as gat_aggregate's."""
     if not isinstance(graph, CSRGraph):
         raise TypeError("gat_layer expects a CSRGraph")
     fo = h.shape[1] // heads
     if fo * heads != h.shape[1] or head_width_padded(fo, h.dtype, pow2=False) != fo:
         raise ValueError("per-head width %d is not a whole number of 16-byte vectors" % fo)
-    return _GatLayerStrided.apply(h, A, graph, heads, fo, alpha, apply_elu, pack_scores)
+    return _GatLayerStrided.apply(h, A, graph, heads, fo, alpha, apply_elu, pack_scores, dropout_p, dropout_seed)
 
 
 # ------------------------------------------------------------------------------------------------ split launches

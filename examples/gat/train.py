@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--classes", type=int, default=47)
     ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--dropout", type=float, default=0.0, help="input and attention dropout (the reference trains with 0.6); the "
+                    "attention mask is drawn inside the gather kernels")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("this example runs the HIP kernels: a GPU is required")
@@ -34,7 +36,7 @@ def main():
     n = graph.n_rows
     labels = ((torch.arange(n, device=dev) * 64 // n) % args.classes).long()      # the planted community (64 blocks)
     x = (torch.randn(n, args.feats, device=dev) + torch.nn.functional.one_hot(labels % args.feats, args.feats) * 2.0).to(torch.bfloat16)
-    model = dnn.SpGAT(args.feats, args.hidden, args.classes, dropout=0.0, alpha=0.2, nheads=args.heads).to(dev).to(torch.bfloat16)
+    model = dnn.SpGAT(args.feats, args.hidden, args.classes, dropout=args.dropout, alpha=0.2, nheads=args.heads).to(dev).to(torch.bfloat16)
     opt = torch.optim.Adam(model.parameters(), lr=2e-3)
     for epoch in range(args.epochs):
         torch.cuda.synchronize()

@@ -248,6 +248,42 @@ int dgll_hip_gat_bwd_cols_strided(void* stream, const dgll_csr_plan* t_plan, con
                                   void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
                                   int fo, float alpha, void* workspace, size_t workspace_bytes,
                                   const float* attn1, const float* attn2, const float* grad_S_rows);
+/* The three strided passes with ATTENTION DROPOUT drawn in the kernels (gatconv.py:132: the row sum keeps every edge, the aggregation
+ * loses a fraction p of them, survivors scaled by 1 / (1 - p)).  The multiplier of edge (row i, column j), head k is a pure function of
+ * (seed, i, j, k) that each pass evaluates for the edges it walks -- no [nnz, heads] mask exists, forward or backward; the transposed
+ * pass swaps the ids back.  Duplicate (i, j) entries of an adjacency that is not coalesced share a draw.
+ *   p      in [0, 1): anything else is DGLL_ERR_INVALID;
+ *   seed   DEVICE pointer to two 32-bit words, read by the kernels: a captured graph whose seed words are rewritten between replays
+ *          draws a fresh mask on every replay.  The backward passes must be given the words the forward read.
+ * Forward and rows pass: T (with t_stride) as dgll_hip_gat_fwd_strided, or NULL T and attn2 as dgll_hip_gat_fwd_rowscore (n_cols = rows
+ * of H; node ids are 32-bit).  There is no in-row form with dropout: a T slot in the padding of the H rows is read as a strided
+ * array.  Everything else as the entry points without dropout.                                                                   */
+int dgll_hip_gat_fwd_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
+                             const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* attn2,
+                             void* out, int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int64_t n_cols, int heads,
+                             int fo, float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
+                             const uint32_t* seed);
+int dgll_hip_gat_bwd_rows_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
+                                  const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
+                                  const float* attn2, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
+                                  int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
+                                  int sd_stride, float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo,
+                                  float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
+                                  const uint32_t* seed);
+int dgll_hip_gat_bwd_cols_dropout(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
+                                  const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
+                                  int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
+                                  void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
+                                  int fo, float alpha, void* workspace, size_t workspace_bytes,
+                                  const float* attn1, const float* attn2, const float* grad_S_rows, double p,
+                                  const uint32_t* seed);
+/* out[k * heads + h] = that multiplier for every nonzero k of a CSR and every head: fp32 [nnz, heads], exactly 0 or (float)(1 / (1 - p)).
+ * The device and the host form evaluate the same function and agree bit for bit (the host form takes host pointers and needs no GPU).
+ * For tests and for callers that want the mask as an array (dgll_hip_gat_fwd's edge_scale); training never calls them.              */
+int dgll_hip_gat_dropout_mask(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads,
+                              const uint32_t* seed, double p, float* out);
+int dgll_host_gat_dropout_mask(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads, const uint32_t* seed,
+                               double p, float* out);
 int dgll_hip_gat_bwd_strided(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,
                              const int64_t* rowptr, const int32_t* col, const int64_t* t_rowptr, const int32_t* t_col,
                              const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
