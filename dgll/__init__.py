@@ -1,5 +1,5 @@
 """Drop-in `dgll` namespace: the reference's import paths (`from dgll import backend as F`,
-`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.dataloader`) resolved onto
+`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.dataloader`, `dgll.embedding`) resolved onto
 the MI355X-native implementation in dgll_amd.  /root/reference/dgll/__init__.py:1 is `import torch as backend`;
 here `backend` is dgll_amd.backend (torch + the missing aliases + HIP aggregation)."""
 import importlib
@@ -26,8 +26,10 @@ _ALIASES = {
     "dgll.sampling.dgllsampler": "dgll_amd.sampling.dgllsampler",
     "dgll.sampling.layerwise": "dgll_amd.sampling.layerwise",
     "dgll.dataloader": "dgll_amd.dataloader",
+    "dgll.embedding": "dgll_amd.embedding",
 }
 for _alias, _target in _ALIASES.items():
     sys.modules[_alias] = importlib.import_module(_target)
 nn = sys.modules["dgll.nn"]
+embedding = sys.modules["dgll.embedding"]      # `import dgll.embedding` finds the alias in sys.modules and binds no attribute itself
 __version__ = dgll_amd.__version__

@@ -659,6 +659,39 @@ int dgll_hip_lw_block_fill(void* stream, const int64_t* rowptr, const int32_t* c
 int dgll_host_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
 
 
+/* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
+ * Every random word is Philox4x32-10 with key = {seed lo, seed hi}.
+ * Walks: CSR (int64 rowptr, int32 col, rows ascending when p or q != 1; edge values do not exist here: walks are unweighted)
+ * over n_nodes nodes, every row shorter than 2^32; starts int64[n]; walks int32[n, length] row-major, walks[i, 0] = starts[i].
+ * A node without out-edges ends the walk: every later entry is -1.  Walk i has the global index g = first_walk_index + i and step
+ * s >= 1, attempt a >= 0 use the counter {g lo, g hi, s, a}: word 0 picks the candidate col[rowptr[v] + mulhi32(x0, deg)], word 1
+ * accepts it when x1 < T (64-bit compare), T = round(2^32 w / M) computed here in float64 with w = 1/p when the candidate is the
+ * previous node, 1 when it is an out-neighbour of the previous node, 1/q otherwise, and M = max(1/p, 1, 1/q).  The first step,
+ * and every step when p == q == 1, takes attempt 0.  After max_attempts (>= 1024) rejections the last candidate is taken and
+ * counted in info[0]; info[1] collects error bits (1: a start outside [0, n_nodes), 2: a column id outside it; that walk ends).
+ * info: int64[2], zeroed by the caller.                                                                                       */
+int dgll_hip_random_walk(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_nodes, const int64_t* starts, int64_t n,
+                         int length, uint64_t first_walk_index, uint64_t seed, double p, double q, int max_attempts, int32_t* walks,
+                         int64_t* info);
+/* The three thresholds of dgll_hip_random_walk, {return, common neighbour, far} (host; for tests and restatements).            */
+int dgll_host_node2vec_thresholds(double p, double q, uint64_t* out3);
+/* Pairs of a batch of walks: centre = position j of walk w, context slot s in [0, 2 window) = position j + o, o = -window..-1,
+ * 1..window; the pair exists when both positions lie in the walk and hold ids in [0, n_nodes).  Negative k of a pair is
+ * searchsorted(cdf, x0, side = right) with cdf uint64[n_nodes] the noise distribution's cumulative sums scaled to 2^32
+ * (cdf[n_nodes - 1] = 2^32) and x0 word 0 of the counter {g lo, g hi, j * 2 window + s, k | 2^31}.
+ * out: int32[n, length, 2 window, negatives], -1 where there is no pair.                                                       */
+int dgll_hip_sgns_negatives(void* stream, const int32_t* walks, int64_t n, int length, int window, int negatives,
+                            const uint64_t* cdf, int64_t n_nodes, uint64_t first_walk_index, uint64_t seed, int32_t* out);
+/* One batch-synchronous SGD step on sum_pairs [-log sigma(u_c . v_t) - sum_k log sigma(-u_c . v_nk)], u = rows of w_in, v = rows of
+ * w_out (both fp32 [n_nodes, dim] row-major, updated in place by fp32 atomics), every gradient at the weights as the step found
+ * them; a negative equal to its pair's context has coefficient 0.  *loss (fp64, device) receives the loss sum.  Scratch:
+ * g_scratch fp32 and target_scratch int32 [n * length * 2 window * (1 + negatives)], delta_scratch fp32 [n * length * dim].
+ * dim in [1, 4032].                                                                                                            */
+int dgll_hip_sgns_step(void* stream, float* w_in, float* w_out, int64_t n_nodes, int dim, const int32_t* walks, int64_t n, int length,
+                       int window, int negatives, const uint64_t* cdf, uint64_t first_walk_index, uint64_t seed, float lr,
+                       float* g_scratch, int32_t* target_scratch, float* delta_scratch, double* loss);
+
+
 /* ---- a10: H = relu(A_csr . (X[:, :actual_F] . W[:actual_F, :])) --------------------------------------------
  * launch_gcn_fused_kernel is the reference's own symbol with its exact signature
  * (/root/reference/dgll/FusedKernel/gcn_fused_kernel.cu:190-195, bound at gcn_extension.cpp:5-10,46-55): int32 CSR,
