@@ -46,6 +46,13 @@ class SpmmChoice(C.Structure):
                [("row_blocks", C.c_int64), ("chunk_blocks", C.c_int64)]
 
 
+class GatChoice(C.Structure):
+    """include/dgll_hip.h: struct dgll_gat_choice (dgll_hip_debug_gat_choice)."""
+    _fields_ = [(n, C.c_int) for n in ("generation", "kind", "trow", "drop", "inrow", "epv", "lpr", "nh", "lph", "unroll", "grid_y",
+                                       "rows_per_wave", "finalize", "error")] + \
+               [("row_blocks", C.c_int64), ("chunk_blocks", C.c_int64), ("message", C.c_char_p)]
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -73,6 +80,7 @@ SIGNATURES = {
     "dgll_hip_device_info": (_i32, [_i32, C.c_char_p, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
     "dgll_hip_debug_tune": (_i32, [_i32, _i32]),
     "dgll_hip_debug_spmm_choice": (_i32, [_i32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "dgll_hip_debug_gat_choice": (_i32, [_i32] * 17 + [_i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     "dgll_hip_csr_plan_create": (_i32, [_vp, _vp, _i64, _i64, _i32, C.POINTER(_vp)]),
     "dgll_hip_csr_plan_destroy": (None, [_vp]),
     "dgll_hip_csr_plan_workspace_bytes": (_sz, [_vp, _i32]),

@@ -17,6 +17,7 @@
 
 #include "common.hpp"
 #include "edge_args.hpp"
+#include "gat_choice.hpp"
 
 namespace dgll {
 
@@ -685,7 +686,7 @@ static bool vec_ok(const void* p, int64_t ld, int esz) { return aligned16(p) && 
 
 }  // namespace dgll
 
-int g_tune_gat_gen = 0;      // dgll_hip_debug_tune(9, v): 1 = first-generation GAT kernels only, 2 = second generation without the in-row form
+dgll::GatTune dgll::g_gat_tune;
 
 using namespace dgll;
 
@@ -721,46 +722,23 @@ DGLL_API size_t dgll_hip_gat_workspace_bytes(const dgll_csr_plan* plan, int head
     return (size_t)plan->n_chunks * (size_t)gat_ws_ld(heads, fo) * sizeof(float);
 }
 
-// Attach the long-row schedule of `plan` (may be NULL) to the launch arguments and size the grid.
-static int gat_schedule(EdgeArgs& a, const dgll_csr_plan* plan, int64_t n_rows, void* workspace, size_t workspace_bytes,
-                        dim3* grid, int esz) {
-    a.threshold = 0; a.n_chunks = 0; a.chunk_blocks = 0; a.ws = nullptr; a.rows_per_wave = 1;
+// Attach the long-row schedule of `plan` (may be NULL) and its workspace to the launch arguments.
+static int gat_attach_plan(EdgeArgs& a, const dgll_csr_plan* plan, void* workspace, size_t workspace_bytes) {
+    a.threshold = 0; a.n_chunks = 0; a.ws = nullptr;
     a.ws_vec = gat_ws_vec(a.heads, a.fo); a.ws_ld = gat_ws_ld(a.heads, a.fo);
-    if (plan) {
-        DGLL_REQUIRE(plan->n_rows == n_rows, "plan was built for a different CSR");
-        a.threshold = plan->threshold;
-        a.n_chunks = plan->n_chunks;
-        a.chunk_begin = plan->d_chunk_begin; a.chunk_end = plan->d_chunk_end; a.chunk_row = plan->d_chunk_row;
-        if (plan->n_chunks > 0) {
-            const size_t need = dgll_hip_gat_workspace_bytes(plan, a.heads, a.fo);
-            if (!workspace || workspace_bytes < need) {
-                set_error("workspace too small for the plan's long-row partials");
-                return DGLL_ERR_WORKSPACE;
-            }
-            a.ws = static_cast<float*>(workspace);
+    if (!plan) return DGLL_OK;
+    DGLL_REQUIRE(plan->n_rows == a.n_rows, "plan was built for a different CSR");
+    a.threshold = plan->threshold;
+    a.n_chunks = plan->n_chunks;
+    a.chunk_begin = plan->d_chunk_begin; a.chunk_end = plan->d_chunk_end; a.chunk_row = plan->d_chunk_row;
+    if (plan->n_chunks > 0) {
+        const size_t need = dgll_hip_gat_workspace_bytes(plan, a.heads, a.fo);
+        if (!workspace || workspace_bytes < need) {
+            set_error("workspace too small for the plan's long-row partials");
+            return DGLL_ERR_WORKSPACE;
         }
-        a.chunk_blocks = (uint32_t)((plan->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-        // as in spmm.hip: ~96 KiB of gathered bytes per wavefront
-        const double row_bytes = (double)plan->nnz / (double)std::max<int64_t>(n_rows, 1) * a.feat * (double)esz;
-        a.rows_per_wave = std::min(std::max(row_bytes > 0 ? (int)(98304.0 / row_bytes) : 8, 1), 8);
+        a.ws = static_cast<float*>(workspace);
     }
-    const int64_t waves = (n_rows + a.rows_per_wave - 1) / a.rows_per_wave;
-    grid->x = a.chunk_blocks + (uint32_t)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-    return DGLL_OK;
-}
-
-template <typename YT>
-static int gat_finalize(const EdgeArgs& a, const dgll_csr_plan* plan, int kind, hipStream_t s) {
-    if (!plan || plan->n_long == 0) return DGLL_OK;
-    constexpr uintptr_t kStore = 4 * sizeof(YT);      // the wavefront variant stores four columns at once
-    const bool rows_aligned = (a.ldy * (int64_t)sizeof(YT)) % kStore == 0 && (reinterpret_cast<uintptr_t>(a.Y) % kStore) == 0;
-    if (a.heads <= kWave && (kind == 1 || rows_aligned))
-        hipLaunchKernelGGL(gat_long_finalize_wave_kernel<YT>, dim3((uint32_t)((plan->n_long + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), 0, s, a, plan->d_long_row, plan->d_long_chunk0, plan->n_long, kind);
-    else
-        hipLaunchKernelGGL(gat_long_finalize_kernel<YT>, dim3((uint32_t)plan->n_long), dim3(kBlock), 0, s, a, plan->d_long_row,
-                           plan->d_long_chunk0, kind);
-    DGLL_HIP_TRY(hipGetLastError());
     return DGLL_OK;
 }
 
@@ -778,31 +756,6 @@ static int gat_common(EdgeArgs& a, const int64_t* rowptr, const int32_t* col, in
     return DGLL_OK;
 }
 
-// Launch geometry of the second-generation kernels (gat_kernel.hpp): `nh` heads per wavefront on `lpr` = nh * lanes-per-head
-// lanes per row.  They cover sparseGatConv's form -- exp(-leakyrelu), no max subtraction, no attention-dropout multiplier ARRAY
-// (dropout drawn in the kernel is theirs: the *_dropout entry points) -- for any per-head width that is a multiple of the 16-byte
-// vector.  False: the first-generation kernels run.
-static bool gat2_pick(const EdgeArgs& a, int* lpr, int* nh, uint32_t* grid_y) {
-    if (g_tune_gat_gen == 1 || a.edge_scale || a.use_max || a.M) return false;
-    int lph = 1;
-    while (lph < a.vph) lph <<= 1;
-    if (lph > kWave) return false;
-    // blocks of 4 / 8 heads are read as float4s: whole blocks, 16-byte aligned
-    // (row-score form, a.T == NULL: no score row is read at all)
-    const bool vec = a.heads % 4 == 0 && (!a.T || (a.tstride % 4 == 0 && aligned16(a.T))) && (!a.DD || aligned16(a.DD));
-    int n = 1;
-    for (int cand = 8; cand >= 1; cand >>= 1) {
-        if (cand * lph > kWave) continue;
-        if (cand > 2 && !(vec && a.heads % cand == 0)) continue;
-        if (cand > 1 && cand / 2 >= a.heads) continue;      // would leave half the wavefront's heads idle
-        n = cand;
-        break;
-    }
-    while (n * lph < 4) lph <<= 1;                           // at least 4 lanes per row slot (idle lanes inside a head)
-    *lpr = n * lph; *nh = n; *grid_y = (uint32_t)((a.heads + n - 1) / n);
-    return true;
-}
-
 // In-kernel attention dropout (the *_dropout entry points): p in [0, 1) and the device pointer to the two seed words.
 static int gat_drop_args(EdgeArgs& a, double p, const uint32_t* seed) {
     if (!(p >= 0.0 && p < 1.0)) {
@@ -815,28 +768,98 @@ static int gat_drop_args(EdgeArgs& a, double p, const uint32_t* seed) {
     return DGLL_OK;
 }
 
-// One head whose gathered-side scores sit right behind the last column of the gathered rows (same stride): the gather itself
-// can bring them along (gat2_kernel INROW).  `second`: an array that must sit one float after `first` (dd after s), or NULL.
-static bool gat2_inrow(const EdgeArgs& a, int lpr, int nh, int esz, const float* first, const float* second) {
-    if (g_tune_gat_gen == 2 || nh != 1 || a.heads != 1 || a.vph >= lpr) return false;
-    const char* slot = static_cast<const char*>(a.H) + (size_t)a.feat * esz;
-    return reinterpret_cast<const char*>(first) == slot && (int64_t)a.tstride * 4 == a.ldh * esz &&
-           (!second || second == first + 1) && (a.ldh - a.feat) * esz >= (second ? 8 : 4);
+// What gat_choose() looks at, read off the filled launch arguments (and the pointers in them).
+static GatLaunchDesc gat_describe(GatPass pass, const EdgeArgs& a, int dtype, GatRowsPhase phase, const dgll_csr_plan* plan) {
+    const int esz = dtype == DGLL_BF16 ? 2 : 4;
+    GatLaunchDesc d{};
+    d.pass = pass; d.dtype = dtype; d.heads = a.heads; d.fo = a.fo; d.mode = a.use_max;
+    d.edge_scale = a.edge_scale != nullptr;
+    d.rowscore = pass != kGatTransposed && a.attn2 != nullptr;
+    d.drop = a.drop_seed != nullptr;
+    d.phase = phase;
+    d.t_stride = a.tstride;
+    d.t_aligned16 = !a.T || aligned16(a.T); d.dd_aligned16 = !a.DD || aligned16(a.DD);
+    d.sd_out = a.sd_out != nullptr;
+    d.score_epilogue = pass == kGatTransposed && a.attn1 != nullptr;
+    d.score_behind_row = reinterpret_cast<const char*>(a.T) == static_cast<const char*>(a.H) + (size_t)a.feat * esz;
+    d.score_pitch_equal = (int64_t)a.tstride * 4 == a.ldh * esz;
+    d.second_follows = !a.DD || a.DD == a.T + 1;
+    d.pad_bytes = (a.ldh - a.feat) * esz;
+    d.has_plan = plan != nullptr;
+    d.n_rows = a.n_rows;
+    if (plan) { d.nnz = plan->nnz; d.n_chunks = plan->n_chunks; d.n_long = plan->n_long; }
+    d.y_aligned = a.ldy % 4 == 0 && reinterpret_cast<uintptr_t>(a.Y) % (4 * esz) == 0;      // the wavefront finalize kernel stores four columns at once
+    return d;
 }
 
-// Geometry of the first-generation kernels: per-head width a power-of-two number of vectors.
-static int gat1_pick(const EdgeArgs& a, int epv, int* lph, int* lpr, uint32_t* grid_y) {
-    *lph = a.fo / epv;
-    DGLL_REQUIRE((*lph & (*lph - 1)) == 0 && *lph <= 64,
-                 "per-head width / vector must be a power of two <= 64 for the max-subtracted / dropout form (pad on the host)");
-    if (a.tstride != a.heads || a.sd_out) {
-        set_error("strided score arrays need the second-generation kernels (mode 0, no attention dropout)");
-        return DGLL_ERR_UNSUPPORTED;
+// [KIND][TROW][DROP] -> the launch function of that instantiation (gat_*.hip); NULL where kGat2Exists says none exists: gat_choose()
+// has refused those.
+typedef bool (*Gat2Launch)(int, int, int, dim3, hipStream_t, const EdgeArgs&, bool);
+static const Gat2Launch kGat2Launch[4][2][2] = {
+    {{gat2_launch<0, false, false>, gat2_launch<0, false, true>}, {gat2_launch<0, true, false>, gat2_launch<0, true, true>}},
+    {{gat2_launch<1, false, false>, nullptr}, {nullptr, nullptr}},
+    {{gat2_launch<2, false, false>, gat2_launch<2, false, true>}, {nullptr, nullptr}},
+    {{gat2_launch<3, false, false>, gat2_launch<3, false, true>}, {gat2_launch<3, true, false>, gat2_launch<3, true, true>}},
+};
+
+// The first-generation kernels: `lph` lanes per head, unroll 4 forward, 2 backward.
+template <int L>
+static void gat1_launch_lpr(GatPass pass, bool f32, dim3 grid, hipStream_t s, const EdgeArgs& a, int lph) {
+    if (pass == kGatForward) {
+        if (f32) hipLaunchKernelGGL((gat_fwd_kernel<float, float, 4, L, 4>), grid, dim3(kBlock), 0, s, a, lph);
+        else hipLaunchKernelGGL((gat_fwd_kernel<bf16_t, bf16_t, 8, L, 4>), grid, dim3(kBlock), 0, s, a, lph);
+    } else if (pass == kGatRows) {
+        if (f32) hipLaunchKernelGGL((gat_bwd_rows_kernel<float, 4, L, 2>), grid, dim3(kBlock), 0, s, a, lph);
+        else hipLaunchKernelGGL((gat_bwd_rows_kernel<bf16_t, 8, L, 2>), grid, dim3(kBlock), 0, s, a, lph);
+    } else {
+        if (f32) hipLaunchKernelGGL((gat_bwd_cols_kernel<float, float, 4, L, 2>), grid, dim3(kBlock), 0, s, a, lph);
+        else hipLaunchKernelGGL((gat_bwd_cols_kernel<bf16_t, bf16_t, 8, L, 2>), grid, dim3(kBlock), 0, s, a, lph);
     }
-    const int vecs = a.feat / epv;
-    *lpr = pick_lpr(vecs);
-    if (*lpr < *lph) *lpr = *lph;
-    *grid_y = (uint32_t)((vecs + *lpr - 1) / *lpr);
+}
+
+template <typename YT>
+static void gat_finalize(const GatChoice& c, const EdgeArgs& a, const dgll_csr_plan* plan, int pass, hipStream_t s) {
+    if (c.finalize == kGatFinalizeWave)
+        hipLaunchKernelGGL(gat_long_finalize_wave_kernel<YT>, dim3((uint32_t)((plan->n_long + kWavesPerBlock - 1) / kWavesPerBlock)),
+                           dim3(kBlock), 0, s, a, plan->d_long_row, plan->d_long_chunk0, plan->n_long, pass);
+    else
+        hipLaunchKernelGGL(gat_long_finalize_kernel<YT>, dim3((uint32_t)plan->n_long), dim3(kBlock), 0, s, a, plan->d_long_row,
+                           plan->d_long_chunk0, pass);
+}
+
+// The common tail of the three passes, `a` filled: the plan's schedule, the choice, the launch it names, the long rows' second launch.
+static int gat_run(void* stream, GatPass pass, EdgeArgs& a, int dtype, const dgll_csr_plan* plan, void* workspace, size_t workspace_bytes,
+                   GatRowsPhase phase = kGatRowsStoredFirst, float* part3 = nullptr) {
+    int rc = gat_attach_plan(a, plan, workspace, workspace_bytes);
+    if (rc != DGLL_OK) return rc;
+    const GatChoice c = gat_choose(gat_describe(pass, a, dtype, phase, plan), g_gat_tune);
+    if (c.error != DGLL_OK) {
+        set_error(c.message);
+        return c.error;
+    }
+    a.chunk_blocks = (uint32_t)c.chunk_blocks; a.rows_per_wave = c.rows_per_wave;
+    if (pass == kGatRows) {
+        gat_rows_phase_args(a, phase, c.generation);
+        DGLL_REQUIRE(a.exact_dd < 2 || part3, "a split exact rows pass needs the [n_rows, 3 * heads] partial-sum buffer");
+        a.part3 = c.generation == 2 ? part3 : nullptr;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((uint32_t)(c.chunk_blocks + c.row_blocks), (uint32_t)c.grid_y, 1);
+    if (c.generation == 2) {
+        if (!kGat2Launch[c.kind][c.trow][c.drop](dtype, c.lpr, c.nh, grid, s, a, c.inrow != 0)) {
+            set_error("no second-generation GAT kernel for this head layout");
+            return DGLL_ERR_UNSUPPORTED;
+        }
+    } else {
+#define CALL(L) gat1_launch_lpr<L>(pass, dtype == DGLL_F32, grid, s, a, c.lph);
+        DGLL_LPR_SWITCH(c.lpr, CALL)
+#undef CALL
+    }
+    DGLL_HIP_TRY(hipGetLastError());
+    if (c.finalize == kGatFinalizeNone) return DGLL_OK;
+    if (pass == kGatRows || dtype == DGLL_F32) gat_finalize<float>(c, a, plan, pass, s);
+    else gat_finalize<bf16_t>(c, a, plan, pass, s);
+    DGLL_HIP_TRY(hipGetLastError());
     return DGLL_OK;
 }
 
@@ -864,40 +887,13 @@ static int gat_fwd_impl(void* stream, const dgll_csr_plan* plan, const int64_t* 
         if (rc != DGLL_OK) return rc;
     }
     DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs a rowmax output");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4, epv = 16 / esz;
+    const int esz = dtype == DGLL_BF16 ? 2 : 4;
     DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && ldh >= a.feat && ldo >= a.feat, "H/out must be 16-byte aligned");
     a.H = H; a.ldh = ldh; a.S = S; a.T = T; a.tstride = t_stride > 0 ? t_stride : heads; a.edge_scale = edge_scale; a.Y = out; a.ldy = ldo;
     a.out_a = rowsum; a.out_b = mode == 1 ? rowmax : nullptr;
     DGLL_REQUIRE(mode == 0 || (!raw && !accumulate), "split (raw / accumulate) launches support mode 0 only");
     a.raw = raw; a.accumulate = accumulate;
-    dim3 grid(1, 1, 1);
-    rc = gat_schedule(a, plan, n_rows, workspace, workspace_bytes, &grid, esz);
-    if (rc != DGLL_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int lpr, nh, lph;
-    if (drop) {
-        if (!gat2_pick(a, &lpr, &nh, &grid.y) || !(attn2 ? gat2_launch_0rd(dtype, lpr, nh, grid, s, a) : gat2_launch_0d(dtype, lpr, nh, grid, s, a))) {
-            set_error("no second-generation GAT kernel with dropout for this head layout");
-            return DGLL_ERR_UNSUPPORTED;
-        }
-    } else if (attn2) {
-        if (!gat2_pick(a, &lpr, &nh, &grid.y) || !gat2_launch_0r(dtype, lpr, nh, grid, s, a)) {
-            set_error("no row-score GAT kernel for this head layout");
-            return DGLL_ERR_UNSUPPORTED;
-        }
-    } else if (gat2_pick(a, &lpr, &nh, &grid.y)) {
-        if (!gat2_launch_0(dtype, lpr, nh, grid, s, a, gat2_inrow(a, lpr, nh, esz, a.T, nullptr))) { set_error("no second-generation GAT kernel for this head layout"); return DGLL_ERR_UNSUPPORTED; }
-    } else {
-        rc = gat1_pick(a, epv, &lph, &lpr, &grid.y);
-        if (rc != DGLL_OK) return rc;
-#define CALL(L)                                                                                                                \
-    if (dtype == DGLL_F32) hipLaunchKernelGGL((gat_fwd_kernel<float, float, 4, L, 4>), grid, dim3(kBlock), 0, s, a, lph);      \
-    else hipLaunchKernelGGL((gat_fwd_kernel<bf16_t, bf16_t, 8, L, 4>), grid, dim3(kBlock), 0, s, a, lph);
-        DGLL_LPR_SWITCH(lpr, CALL)
-#undef CALL
-    }
-    DGLL_HIP_TRY(hipGetLastError());
-    return dtype == DGLL_F32 ? gat_finalize<float>(a, plan, 0, s) : gat_finalize<bf16_t>(a, plan, 0, s);
+    return gat_run(stream, kGatForward, a, dtype, plan, workspace, workspace_bytes);
 }
 
 DGLL_API int dgll_hip_gat_fwd(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
@@ -938,9 +934,8 @@ DGLL_API int dgll_hip_gat_fwd_rowscore(void* stream, const dgll_csr_plan* plan, 
                         alpha, apply_elu, 0, workspace, workspace_bytes, raw, accumulate, attn2);
 }
 
-// Pass 1 of the backward (rows of A or of one column-half of A): DN, DD and grad_S.  accumulate: 0 = first (or only) launch:
-// writes DN, DD, grad_S, dd_i from the stored output row; 1 = a further launch over another column half (grad_S +=); 3 = DECLARED
-// the only launch over these rows (second-generation kernels: exact dd_i from the pass's own dot products, gat_kernel.hpp).
+// Pass 1 of the backward (rows of A or of one column-half of A): DN, DD and grad_S.  accumulate: the C ABI's value of a GatRowsPhase
+// (edge_args.hpp).
 static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
                              const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* edge_scale,
                              const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
@@ -962,45 +957,14 @@ static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int6
         if (rc != DGLL_OK) return rc;
     }
     DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs the forward's rowmax");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4, epv = 16 / esz;
+    const int esz = dtype == DGLL_BF16 ? 2 : 4;
     DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && vec_ok(grad_out, ldg, esz) && vec_ok(dn, ldn, esz),
                  "matrices must be 16-byte aligned with padded leading dimensions");
     a.H = H; a.ldh = ldh; a.S = S; a.T = T; a.tstride = t_stride > 0 ? t_stride : heads; a.M = mode == 1 ? rowmax : nullptr;
     a.DEN = rowsum; a.edge_scale = edge_scale;
     a.G = grad_out; a.ldg = ldg; a.O = out; a.ldo = ldo; a.Y = dn; a.ldy = ldn; a.out_a = grad_S; a.out_b = dd;
     a.sd_out = sd_out; a.sd_stride = sd_stride;
-    a.accumulate = accumulate;
-    dim3 grid(1, 1, 1);
-    rc = gat_schedule(a, plan, n_rows, workspace, workspace_bytes, &grid, esz);
-    if (rc != DGLL_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int lpr, nh, lph;
-    if (gat2_pick(a, &lpr, &nh, &grid.y)) {
-        // 3: declared the only launch over these rows; 4 / 5 / 6: first / middle / last launch of a split exact pass (part3 carries
-        // the partial sums): dd_i from the pass's own dot products
-        a.exact_dd = accumulate == 3 ? 1 : (accumulate >= 4 && accumulate <= 6) ? accumulate - 2 : 0;
-        DGLL_REQUIRE(a.exact_dd < 2 || part3, "a split exact rows pass needs the [n_rows, 3 * heads] partial-sum buffer");
-        a.part3 = part3;
-        a.accumulate = accumulate == 1 ? 1 : 0;
-        const bool inrow = !attn2 && gat2_inrow(a, lpr, nh, esz, a.T, nullptr);
-        const bool ok = drop ? (attn2 ? gat2_launch_3rd(dtype, lpr, nh, grid, s, a) : gat2_launch_3d(dtype, lpr, nh, grid, s, a))
-                      : attn2 ? gat2_launch_3r(dtype, lpr, nh, grid, s, a)
-                              : (a.exact_dd ? gat2_launch_3(dtype, lpr, nh, grid, s, a, inrow) : gat2_launch_1(dtype, lpr, nh, grid, s, a, inrow));
-        if (!ok) { set_error("no second-generation GAT kernel for this head layout"); return DGLL_ERR_UNSUPPORTED; }
-    } else {
-        DGLL_REQUIRE(!attn2 && !drop, "the row-score form and in-kernel dropout need the second-generation kernels");
-        rc = gat1_pick(a, epv, &lph, &lpr, &grid.y);
-        if (rc != DGLL_OK) return rc;
-        DGLL_REQUIRE(dd, "the first-generation rows pass writes dd");
-        a.accumulate = (accumulate == 1 || accumulate == 5 || accumulate == 6) ? 1 : 0;    // first-generation kernels: dd from the stored output row in every mode
-#define CALL(L)                                                                                                              \
-    if (dtype == DGLL_F32) hipLaunchKernelGGL((gat_bwd_rows_kernel<float, 4, L, 2>), grid, dim3(kBlock), 0, s, a, lph);      \
-    else hipLaunchKernelGGL((gat_bwd_rows_kernel<bf16_t, 8, L, 2>), grid, dim3(kBlock), 0, s, a, lph);
-        DGLL_LPR_SWITCH(lpr, CALL)
-#undef CALL
-    }
-    DGLL_HIP_TRY(hipGetLastError());
-    return gat_finalize<float>(a, plan, 1, s);
+    return gat_run(stream, kGatRows, a, dtype, plan, workspace, workspace_bytes, gat_rows_phase(accumulate), part3);
 }
 
 DGLL_API int dgll_hip_gat_bwd_rows(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
@@ -1047,7 +1011,7 @@ static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const in
     DGLL_REQUIRE(dn && Hrow && T_row && S_col && dd_col && grad_H && grad_T, "NULL argument");
     DGLL_REQUIRE(mode == 0 || rowmax_col, "mode 1 needs the forward's rowmax");
     DGLL_REQUIRE(!edge_scale || t_perm, "edge_scale needs the transpose permutation");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4, epv = 16 / esz;
+    const int esz = dtype == DGLL_BF16 ? 2 : 4;
     DGLL_REQUIRE(vec_ok(dn, ldn, esz) && vec_ok(Hrow, ldh, esz) && vec_ok(grad_H, ldgh, esz),
                  "matrices must be 16-byte aligned with padded leading dimensions");
     t.perm = t_perm; t.H = dn; t.ldh = ldn; t.G = Hrow; t.ldg = ldh; t.S = T_row; t.T = S_col; t.DD = dd_col;
@@ -1061,30 +1025,25 @@ static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const in
     }
     t.M = mode == 1 ? rowmax_col : nullptr; t.edge_scale = edge_scale; t.Y = grad_H; t.ldy = ldgh; t.out_a = grad_T;
     t.out_b = nullptr;
-    dim3 grid(1, 1, 1);
-    rc = gat_schedule(t, t_plan, n_rows_t, workspace, workspace_bytes, &grid, esz);
-    if (rc != DGLL_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int lpr, nh, lph;
-    if (drop) {
-        if (!gat2_pick(t, &lpr, &nh, &grid.y) || !gat2_launch_2d(dtype, lpr, nh, grid, s, t)) {
-            set_error("no second-generation GAT kernel with dropout for this head layout");
-            return DGLL_ERR_UNSUPPORTED;
-        }
-    } else if (gat2_pick(t, &lpr, &nh, &grid.y)) {
-        if (!gat2_launch_2(dtype, lpr, nh, grid, s, t, gat2_inrow(t, lpr, nh, esz, t.T, t.DD))) { set_error("no second-generation GAT kernel for this head layout"); return DGLL_ERR_UNSUPPORTED; }
-    } else {
-        rc = gat1_pick(t, epv, &lph, &lpr, &grid.y);
-        if (rc != DGLL_OK) return rc;
-        DGLL_REQUIRE(!attn1, "the score-gradient epilogue needs the second-generation kernels");
-#define CALL(L)                                                                                                                  \
-    if (dtype == DGLL_F32) hipLaunchKernelGGL((gat_bwd_cols_kernel<float, float, 4, L, 2>), grid, dim3(kBlock), 0, s, t, lph);   \
-    else hipLaunchKernelGGL((gat_bwd_cols_kernel<bf16_t, bf16_t, 8, L, 2>), grid, dim3(kBlock), 0, s, t, lph);
-        DGLL_LPR_SWITCH(lpr, CALL)
-#undef CALL
-    }
-    DGLL_HIP_TRY(hipGetLastError());
-    return dtype == DGLL_F32 ? gat_finalize<float>(t, t_plan, 2, s) : gat_finalize<bf16_t>(t, t_plan, 2, s);
+    return gat_run(stream, kGatTransposed, t, dtype, t_plan, workspace, workspace_bytes);
+}
+
+DGLL_API int dgll_hip_debug_gat_choice(int pass, int dtype, int heads, int fo, int mode, int edge_scale, int rowscore, int drop, int phase,
+                                       int t_stride, int t_aligned16, int dd_aligned16, int sd_out, int score_epilogue,
+                                       int score_behind_row, int score_pitch_equal, int second_follows, int64_t pad_bytes, int has_plan,
+                                       int64_t n_rows, int64_t nnz, int64_t n_chunks, int64_t n_long, int y_aligned, dgll_gat_choice* out) {
+    DGLL_REQUIRE(out != nullptr, "out is NULL");
+    DGLL_REQUIRE(pass >= kGatForward && pass <= kGatTransposed && (dtype == DGLL_F32 || dtype == DGLL_BF16) && (mode == 0 || mode == 1),
+                 "pass / dtype / mode");
+    DGLL_REQUIRE(heads > 0 && fo > 0 && fo % (dtype == DGLL_BF16 ? 8 : 4) == 0 && t_stride >= 0 && pad_bytes >= 0 && n_rows > 0 && nnz >= 0 &&
+                 n_chunks >= 0 && n_long >= 0, "bad launch description");
+    const bool plan = has_plan != 0;
+    *out = gat_choose(GatLaunchDesc{(GatPass)pass, dtype, heads, fo, mode, edge_scale != 0, rowscore != 0, drop != 0, gat_rows_phase(phase),
+                                    t_stride > 0 ? t_stride : heads, t_aligned16 != 0, dd_aligned16 != 0, sd_out != 0, score_epilogue != 0,
+                                    score_behind_row != 0, score_pitch_equal != 0, second_follows != 0, pad_bytes, plan, n_rows,
+                                    plan ? nnz : 0, plan ? n_chunks : 0, plan ? n_long : 0, y_aligned != 0}, g_gat_tune);
+    if (out->error != DGLL_OK) set_error(out->message);
+    return out->error;
 }
 
 DGLL_API int dgll_hip_gat_bwd_cols(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr, const int32_t* t_col,

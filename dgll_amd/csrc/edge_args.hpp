@@ -1,4 +1,5 @@
-// edge_args.hpp -- launch arguments and wave-level helpers shared by the per-edge kernels (edge.hip, gat.hip).
+// edge_args.hpp -- launch arguments and wave-level helpers shared by the per-edge kernels (edge.hip; gat_kernel.hpp and the
+// gat_*.hip translation units that instantiate it).
 #pragma once
 #include "common.hpp"
 #include "gat_dropout.hpp"
@@ -153,21 +154,33 @@ __device__ __forceinline__ void for_each_batch(const int32_t* __restrict__ col, 
     }
 }
 
-// gat_fwd.hip / gat_bwd_rows.hip / gat_bwd_cols.hip: second-generation GAT passes (0 forward, 1 backward over the rows of A,
-// 2 backward over the rows of A^T) for `nh` heads per wavefront on `lpr` lanes per row; inrow: the gathered-side scores sit
-// in the padding of the gathered rows and arrive with the gather (one head).  False: no such instantiation.
-bool gat2_launch_0(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);
-bool gat2_launch_0r(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);             // pass 0, scores from the gathered rows
-bool gat2_launch_1(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);
-bool gat2_launch_3(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);   // pass 1, exact-dd form alone
-bool gat2_launch_3r(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);            // pass 1 exact, scores from the gathered rows
-bool gat2_launch_2(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);
-// gat_fwd_drop.hip / gat_fwd_rowscore_drop.hip / gat_bwd_rows_drop.hip / gat_bwd_rows_rowscore_drop.hip / gat_bwd_cols_drop.hip: the
-// same passes with the attention-dropout mask drawn in the kernel (a.drop, a.drop_seed); rows pass: the exact-dd form only
-bool gat2_launch_0d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
-bool gat2_launch_0rd(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
-bool gat2_launch_3d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
-bool gat2_launch_3rd(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
-bool gat2_launch_2d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a);
+// Launches of the rows pass (backward over the rows of A, or of one column half of A).  The values are the C ABI's: `accumulate` of
+// dgll_hip_gat_bwd_rows (0, 1, 3 .. 6; anything else reads as 0), `phase` of dgll_hip_gat_bwd_rows_split (4 .. 6).
+enum GatRowsPhase {
+    kGatRowsStoredFirst = 0,    // dd_i from the stored output row; the first (or only) launch: writes DN, DD, grad_S
+    kGatRowsStoredFurther = 1,  // ... a further launch over another column half (grad_S +=)
+    kGatRowsExactOnly = 3,      // exact dd_i (from the pass's own dot products, gat_kernel.hpp); DECLARED the only launch over these rows
+    kGatRowsExactFirst = 4,     // exact dd_i, split over column halves: the first launch (writes DN; partial sums -> part3)
+    kGatRowsExactMiddle = 5,    // ... a middle one (part3 +=)
+    kGatRowsExactLast = 6,      // ... the last (adds part3, writes dd and grad_S)
+};
+inline GatRowsPhase gat_rows_phase(int abi_value) {
+    return abi_value == 1 || (abi_value >= 3 && abi_value <= 6) ? (GatRowsPhase)abi_value : kGatRowsStoredFirst;
+}
+// EdgeArgs::exact_dd and ::accumulate of a rows-pass launch.  The first-generation kernels (edge.hip) have no exact form: they take
+// dd_i from the stored output row in every phase, and a split pass's middle and last launches add to what the first one wrote.
+inline void gat_rows_phase_args(EdgeArgs& a, GatRowsPhase phase, int generation) {
+    a.exact_dd = generation == 2 && phase >= kGatRowsExactOnly ? phase - 2 : 0;
+    a.accumulate = phase == kGatRowsStoredFurther || (generation == 1 && (phase == kGatRowsExactMiddle || phase == kGatRowsExactLast));
+}
+
+// Second-generation GAT passes (gat2_kernel, gat_kernel.hpp) for `nh` heads per wavefront on `lpr` lanes per row.  KIND: 0 forward,
+// 1 backward over the rows of A with dd_i from the stored output row, 3 the same pass in its exact-dd form alone, 2 backward over the
+// rows of A^T; TROW: t_j formed from the gathered row (row-score form); DROP: the attention-dropout mask drawn in the kernel (a.drop,
+// a.drop_seed); inrow: the gathered-side scores sit in the padding of the gathered rows and arrive with the gather (one head, neither
+// TROW nor DROP).  Defined in gat_kernel.hpp and instantiated explicitly, one or two (KIND, TROW, DROP) per gat_*.hip so that they
+// compile in parallel; gat_choice.hpp lists which exist.  False: no kernel for this (dtype, lpr, nh).
+template <int KIND, bool TROW, bool DROP>
+bool gat2_launch(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow);
 
 }  // namespace dgll

@@ -2,7 +2,5 @@
 #include "gat_kernel.hpp"
 
 namespace dgll {
-bool gat2_launch_2(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
-    return gat2_launch_kind<2>(dtype, lpr, nh, grid, s, a, inrow);
-}
+template bool gat2_launch<2, false, false>(int, int, int, dim3, hipStream_t, const EdgeArgs&, bool);
 }  // namespace dgll

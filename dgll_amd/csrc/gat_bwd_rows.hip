@@ -2,7 +2,5 @@
 #include "gat_kernel.hpp"
 
 namespace dgll {
-bool gat2_launch_1(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
-    return gat2_launch_kind<1>(dtype, lpr, nh, grid, s, a, inrow);
-}
+template bool gat2_launch<1, false, false>(int, int, int, dim3, hipStream_t, const EdgeArgs&, bool);
 }  // namespace dgll

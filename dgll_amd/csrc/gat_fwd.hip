@@ -2,7 +2,5 @@
 #include "gat_kernel.hpp"
 
 namespace dgll {
-bool gat2_launch_0(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
-    return gat2_launch_kind<0>(dtype, lpr, nh, grid, s, a, inrow);
-}
+template bool gat2_launch<0, false, false>(int, int, int, dim3, hipStream_t, const EdgeArgs&, bool);
 }  // namespace dgll

@@ -3,7 +3,5 @@
 #include "gat_kernel.hpp"
 
 namespace dgll {
-bool gat2_launch_0d(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a) {
-    return gat2_launch_kind<0, false, true>(dtype, lpr, nh, grid, s, a, false);
-}
+template bool gat2_launch<0, false, true>(int, int, int, dim3, hipStream_t, const EdgeArgs&, bool);
 }  // namespace dgll

@@ -1,5 +1,6 @@
 // gat_kernel.hpp -- the three gather passes of the fused multi-head GAT layer for gfx950, second generation.
-// Included by gat_fwd.hip / gat_bwd_rows.hip / gat_bwd_cols.hip (one translation unit per pass: they compile in parallel).
+// Included by the gat_*.hip translation units, each of which instantiates gat2_launch<KIND, TROW, DROP> (edge_args.hpp) for one or two
+// forms: they compile in parallel.
 //
 // Reference semantics (under /root/reference/dgll/nn/Convolution/):
 //   sparseGatConv.forward  gatconv.py:111-148   e_ij = exp(-leakyrelu(a1.h_i + a2.h_j)); out_i = sum_j e_ij h_j / sum_j e_ij; elu
@@ -605,8 +606,8 @@ static bool gat2_launch_lpr(const EdgeArgs& a, int lpr, int nh, dim3 grid, hipSt
     }
 }
 
-template <int KIND, bool TROW = false, bool DROP = false>
-static bool gat2_launch_kind(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
+template <int KIND, bool TROW, bool DROP>
+bool gat2_launch(int dtype, int lpr, int nh, dim3 grid, hipStream_t s, const EdgeArgs& a, bool inrow) {
     if (dtype == DGLL_F32) return gat2_launch_lpr<float, float, 4, KIND, TROW, DROP>(a, lpr, nh, grid, s, inrow);
     return gat2_launch_lpr<bf16_t, bf16_t, 8, KIND, TROW, DROP>(a, lpr, nh, grid, s, inrow);
 }

@@ -191,6 +191,13 @@ def gat_dropout_mask(graph, heads, p, seed):
     return out
 
 
+def _rowscore_addressable(h):
+    """The row-score kernels address the gathered rows by 32-bit byte offsets formed with a 24-bit multiply: at most 2^24 rows of
+    less than 2^24 bytes, 4 GB in all.  Mirrors rowscore_addressable() of csrc/edge.hip (its entry points refuse what this would let through)."""
+    row_bytes = h.stride(0) * h.element_size()
+    return h.shape[0] <= (1 << 24) and row_bytes < (1 << 24) and h.shape[0] * row_bytes <= 0xFFFFFFFF
+
+
 def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, attn2=None, dropout=None):
     """Forward gather pass on dgll_hip_gat_fwd_strided.  Returns (h with aligned rows, s, t, out, rowsum, packed).
     attn2: fp32 [heads * fo], a2 of every head laid out like a row of h (t = h . a2 per head): when the scores cannot ride in the rows'
@@ -216,9 +223,7 @@ def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_score
     ws_bytes = int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     timer = _launch_timer()
-    # (the row-score kernel addresses h by 32-bit byte offsets: at most 2^24 rows and 4 GB)
-    row_scores = attn2 is not None and not packed and ROW_SCORES and h.shape[0] <= (1 << 24) and h.stride(0) * esz < (1 << 24) \
-        and h.shape[0] * h.stride(0) * esz <= 0xFFFFFFFF
+    row_scores = attn2 is not None and not packed and ROW_SCORES and _rowscore_addressable(h)
     form = "packed" if packed else ("rowscore" if row_scores else "")
     if dropout is not None:
         form = (form + " dropout").strip()
@@ -287,8 +292,7 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
         a1, a2 = (v.detach().to(torch.float32).contiguous() for v in attn)
     with torch.cuda.device(dev):
         st = _stream(dev)
-        small = h.shape[0] <= (1 << 24) and h.stride(0) * esz < (1 << 24) and h.shape[0] * h.stride(0) * esz <= 0xFFFFFFFF
-        rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and small
+        rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and _rowscore_addressable(h)
         end = timer.start(("gat", "bwd_rows") + (tag[:4] + (("rowscore " + tag[4]).strip(),) if rows_rowscore else tag), dev) if timer else None
         if dropout is not None:
             code = _lib.lib.dgll_hip_gat_bwd_rows_dropout(

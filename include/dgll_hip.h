@@ -63,6 +63,28 @@ int dgll_hip_debug_spmm_choice(int x_dtype, int y_dtype, int feat, int64_t n_row
                                int64_t n_chunks, int64_t n_flat, int weighted, int accumulate, int gate, int aligned16,
                                int only_long, struct dgll_spmm_choice* out);
 
+/* Diagnostics only, touches no device: the kernel a launch of the fused GAT passes of this description gets under the current
+ * knobs (key 9) -- the launch path calls the same function.  In: pass 0 forward / 1 rows of A / 2 rows of A^T; rowscore: attn2
+ * INSTEAD of T; drop: dropout drawn in the kernel; phase: the rows pass's `accumulate` / `phase`; t_stride (0 = heads) and the
+ * 16-byte alignment of the gathered-side score arrays (T; pass 2: S and dd of the columns); sd_out / score_epilogue: those
+ * optional outputs are asked for; the in-row facts: the first score array starts right behind the first gathered row's last
+ * column, t_stride floats are one row pitch, the second array (pass 2) sits one float after the first, pad_bytes of padding per
+ * gathered row; nnz / n_chunks / n_long are the plan's (ignored when has_plan is 0); y_aligned: the output rows admit the
+ * wavefront finalize kernel's four-column stores.
+ * Out: generation 1 / 2; generation 2: gat2_kernel<.., lpr, nh, 4, kind, inrow, trow, drop>; generation 1: lph lanes per head,
+ * `unroll` gathers in flight; the grid is (chunk_blocks + row_blocks, grid_y); finalize: 0 none, 1 a wavefront, 2 a workgroup
+ * per long row.  A refusal returns its code (also in `error`) with `message` (static storage) as the error text.          */
+struct dgll_gat_choice {
+    int generation, kind, trow, drop, inrow, epv, lpr, nh, lph, unroll, grid_y, rows_per_wave, finalize, error;
+    int64_t row_blocks, chunk_blocks;
+    const char* message;
+};
+int dgll_hip_debug_gat_choice(int pass, int dtype, int heads, int fo, int mode, int edge_scale, int rowscore, int drop, int phase,
+                              int t_stride, int t_aligned16, int dd_aligned16, int sd_out, int score_epilogue,
+                              int score_behind_row, int score_pitch_equal, int second_follows, int64_t pad_bytes, int has_plan,
+                              int64_t n_rows, int64_t nnz, int64_t n_chunks, int64_t n_long, int y_aligned,
+                              struct dgll_gat_choice* out);
+
 /* ---- CSR schedule ----------------------------------------------------------------------------------
  * Built once per adjacency structure (the reference builds its adjacency once per graph,
  * nn/utils/utils.py:171,179).  Rows longer than `long_row_threshold` nonzeros (<= 0 selects the default,
