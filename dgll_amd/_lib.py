@@ -204,10 +204,12 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 
 # ---- launch plumbing shared by the Python wrappers ---------------------------------------------------------------------------
-# A wrapper needs two things from torch per launch: the raw stream the caller is on and the guarantee that the tensor's device is
-# current.  torch.cuda.current_stream() builds a Stream object (2-4 us) and `with torch.cuda.device(d)` a context object (3-4 us):
-# of the ~25 us a launch costs through Python that is a third, and the consumer thread of the mini-batch pipeline issues ~80 launches
-# per 2 ms batch.  Both are replaced by their cheap cores.
+# Every stream-taking entry point is called through `launch`: device current, raw stream, optional LaunchTimer bracket, the call,
+# the error check under the name of the entry that ran.  From torch a launch needs the raw stream the caller is on and the guarantee
+# that the tensor's device is current.  torch.cuda.current_stream() builds a Stream object (2-4 us) and `with torch.cuda.device(d)` a
+# context object (3-4 us): of the ~25 us a launch costs through Python that is a third, and the consumer thread of the mini-batch
+# pipeline issues ~80 launches per 2 ms batch.  `launch` uses their cheap cores (`raw_stream`, `on_device`) and builds a Stream
+# object only for the events of an active timer.
 _NULL_CTX = contextlib.nullcontext()
 
 
@@ -223,6 +225,63 @@ def on_device(device):
     if idx is None or idx == torch.cuda.current_device():
         return _NULL_CTX
     return torch.cuda.device(idx)
+
+
+def ptr(t):
+    """t.data_ptr(), None (a NULL argument) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def pitch(t):
+    """t.stride(0), the row pitch in elements; 0 for None."""
+    return 0 if t is None else t.stride(0)
+
+
+class LaunchTimer:
+    """HIP-event timing of individual kernel launches on the stream they are issued on (bench.py's roofline leg).
+    Usage: `with LaunchTimer() as t: ...steps...` then t.summary() -> {tag: (count, avg_ms)}."""
+    active = None
+
+    def __init__(self):
+        self.records = []
+
+    def __enter__(self):
+        LaunchTimer.active = self
+        return self
+
+    def __exit__(self, *exc):
+        LaunchTimer.active = None
+
+    def start(self, tag, stream):
+        """Record the opening event on `stream`; the caller records the returned closing event there after the launch."""
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        self.records.append((tag, a, b))
+        return b
+
+    def summary(self):
+        torch.cuda.synchronize()
+        out = {}
+        for tag, a, b in self.records:
+            n, tot = out.get(tag, (0, 0.0))
+            out[tag] = (n + 1, tot + a.elapsed_time(b))
+        return {k: (n, tot / n) for k, (n, tot) in out.items()}
+
+
+def launch(name, device, *args, tag=None, stream=None):
+    """lib.<name>(stream, *args) on `device`, checked.  stream: a torch stream, None = the current one of `device`.  tag: the launch's
+    LaunchTimer key, or a zero-argument callable that builds it (called only while a timer is active)."""
+    timer = LaunchTimer.active if tag is not None else None
+    with on_device(device):
+        raw = raw_stream(device) if stream is None else stream.cuda_stream
+        if timer is None:
+            code = getattr(lib, name)(raw, *args)
+        else:
+            on = torch.cuda.current_stream(device) if stream is None else stream
+            end = timer.start(tag() if callable(tag) else tag, on)
+            code = getattr(lib, name)(raw, *args)
+            end.record(on)
+    check(code, name)
 
 
 def last_error():

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .ranges import rng
-from .ops import _dtype_code
+from .ops import _dtype_code, alloc_features
 
 
 # Row pitches (bytes) of the pinned host store and of the HBM cache block; 1 = the rows' natural pitch (the default).  Measured, round 6
@@ -194,10 +194,7 @@ class GraphCacheServer:
             if out is None:
                 # rows start on 16-byte boundaries (602 bf16 columns -> a leading dimension of 608): what consumes them -- the
                 # MFMA transform, the split-K weight gradient -- then reads them as they are instead of re-laying them out
-                epv = 16 // self.features.element_size()
-                ld = -(-self.total_dim // epv) * epv
-                store = torch.empty((n, ld), dtype=self.features.dtype, device=self.device)
-                out = store[:, :self.total_dim] if ld != self.total_dim else store
+                out = alloc_features(n, self.total_dim, self.features.dtype, self.device, pad_to=16 // self.features.element_size())
             if n == 0:
                 return out
             with self._pending_lock:
@@ -209,14 +206,10 @@ class GraphCacheServer:
             counter = None
             if self.log and use_map:
                 counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-            with torch.cuda.device(self.device), rng("cache-gpu"):
-                code = _lib.lib.dgll_hip_gather_rows_mapped(
-                    stream.cuda_stream, cache.data_ptr() if use_map else None, cache.stride(0) if use_map else 0,
-                    self.features.data_ptr(), self.features.stride(0), nids.data_ptr(),
-                    slot_map.data_ptr() if use_map else None,
-                    host_map.data_ptr() if host_map is not None else None, out.data_ptr(), out.stride(0), n,
-                    self.total_dim, _dtype_code(out), counter.data_ptr() if counter is not None else None)
-            _lib.check(code, "dgll_hip_gather_rows_mapped")
+            with rng("cache-gpu"):
+                _lib.launch("dgll_hip_gather_rows_mapped", self.device, _lib.ptr(cache), _lib.pitch(cache), self.features.data_ptr(),
+                            self.features.stride(0), nids.data_ptr(), _lib.ptr(slot_map), _lib.ptr(host_map), out.data_ptr(),
+                            out.stride(0), n, self.total_dim, _dtype_code(out), _lib.ptr(counter), stream=stream)
             if use_map:                           # a refresh may drop the pair while this gather still runs on `stream`
                 slot_map.record_stream(stream)
                 cache.record_stream(stream)
@@ -247,7 +240,7 @@ class GraphCacheServer:
                 host_map = self.nid_map
                 counter = torch.zeros(1, dtype=torch.int64, device=self.device) if (self.log and use_map) else None
             total = 0
-            with torch.cuda.device(self.device), rng("cache-gpu"):
+            with rng("cache-gpu"):
                 for nids, out in zip(nids_list, outs):
                     n = int(nids.numel())
                     if n == 0:
@@ -255,13 +248,9 @@ class GraphCacheServer:
                     if out.shape[0] != n or out.shape[1] != self.total_dim or out.stride(1) != 1 or out.dtype != self.features.dtype:
                         raise ValueError("fetch_data_into: every output block is [len(ids), D] of the feature dtype, unit column stride")
                     total += n
-                    code = _lib.lib.dgll_hip_gather_rows_mapped(
-                        stream.cuda_stream, cache.data_ptr() if use_map else None, cache.stride(0) if use_map else 0,
-                        self.features.data_ptr(), self.features.stride(0), nids.data_ptr(),
-                        slot_map.data_ptr() if use_map else None, host_map.data_ptr() if host_map is not None else None,
-                        out.data_ptr(), out.stride(0), n, self.total_dim, _dtype_code(out),
-                        counter.data_ptr() if counter is not None else None)
-                    _lib.check(code, "dgll_hip_gather_rows_mapped")
+                    _lib.launch("dgll_hip_gather_rows_mapped", self.device, _lib.ptr(cache), _lib.pitch(cache), self.features.data_ptr(),
+                                self.features.stride(0), nids.data_ptr(), _lib.ptr(slot_map), _lib.ptr(host_map), out.data_ptr(),
+                                out.stride(0), n, self.total_dim, _dtype_code(out), _lib.ptr(counter), stream=stream)
             if use_map:
                 slot_map.record_stream(stream)
                 cache.record_stream(stream)
@@ -287,9 +276,8 @@ class GraphCacheServer:
         if self.log and use_map:
             with torch.cuda.stream(stream):          # zeroed on the stream whose kernels add to it (not on the caller's current stream)
                 counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-        return (cache.data_ptr() if use_map else None, cache.stride(0) if use_map else 0, self.features.data_ptr(), self.features.stride(0),
-                slot_map.data_ptr() if use_map else None, self.nid_map.data_ptr() if self.nid_map is not None else None, counter,
-                (slot_map, cache))
+        return (_lib.ptr(cache), _lib.pitch(cache), self.features.data_ptr(), self.features.stride(0), _lib.ptr(slot_map),
+                _lib.ptr(self.nid_map), counter, (slot_map, cache))
 
     def native_load_end(self, stream, counter, keep, tries, done=None):
         slot_map, cache = keep
@@ -317,12 +305,8 @@ class GraphCacheServer:
             rowptr = rowptr.to(self.device, dtype=torch.int64, non_blocking=True)
             n_rows = int(rowptr.numel()) - 1
             esz = self.features.element_size()
-            epv = 16 // esz
-            ld = -(-self.total_dim // epv) * epv
             if out is None:
-                store = torch.zeros((n_rows, ld), dtype=self.features.dtype, device=self.device) if ld != self.total_dim else \
-                    torch.empty((n_rows, ld), dtype=self.features.dtype, device=self.device)
-                out = store[:, :self.total_dim] if ld != self.total_dim else store
+                out = alloc_features(n_rows, self.total_dim, self.features.dtype, self.device, pad_to=16 // esz, zero_pad=True)
             elif out.shape[0] != n_rows or out.shape[1] != self.total_dim or out.stride(1) != 1:
                 raise ValueError("aggregate_data(out=): [len(rowptr) - 1, D] rows, unit column stride")
             if n_rows <= 0:
@@ -338,14 +322,11 @@ class GraphCacheServer:
             counter = None
             if self.log and use_map:
                 counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-            with torch.cuda.device(self.device), rng("cache-gpu"):
-                code = _lib.lib.dgll_hip_aggregate_rows_mapped(
-                    stream.cuda_stream, cache.data_ptr() if use_map else None, cache.stride(0) if use_map else 0,
-                    self.features.data_ptr(), self.features.stride(0), nids.data_ptr(),
-                    slot_map.data_ptr() if use_map else None, host_map.data_ptr() if host_map is not None else None,
-                    rowptr.data_ptr(), out.data_ptr(), out.stride(0), n_rows, self.total_dim, _dtype_code(out),
-                    _lib.REDUCE_MEAN if reduce == "mean" else _lib.REDUCE_SUM, counter.data_ptr() if counter is not None else None)
-            _lib.check(code, "dgll_hip_aggregate_rows_mapped")
+            with rng("cache-gpu"):
+                _lib.launch("dgll_hip_aggregate_rows_mapped", self.device, _lib.ptr(cache), _lib.pitch(cache), self.features.data_ptr(),
+                            self.features.stride(0), nids.data_ptr(), _lib.ptr(slot_map), _lib.ptr(host_map), rowptr.data_ptr(),
+                            out.data_ptr(), out.stride(0), n_rows, self.total_dim, _dtype_code(out),
+                            _lib.REDUCE_MEAN if reduce == "mean" else _lib.REDUCE_SUM, _lib.ptr(counter), stream=stream)
             if use_map:
                 slot_map.record_stream(stream)
                 cache.record_stream(stream)
@@ -384,13 +365,7 @@ def gather_rows(x, idx, out=None):
     """x[idx] for a device (or pinned host) matrix x through the HIP gather kernel (dgraph.py:105)."""
     dev = idx.device
     if out is None:
-        epv = 16 // x.element_size()
-        ld = -(-x.shape[1] // epv) * epv
-        store = torch.empty((idx.numel(), ld), dtype=x.dtype, device=dev)
-        out = store[:, :x.shape[1]] if ld != x.shape[1] else store
-    with torch.cuda.device(dev):
-        code = _lib.lib.dgll_hip_gather_rows(torch.cuda.current_stream(dev).cuda_stream, None, 0, x.data_ptr(), x.stride(0),
-                                             idx.data_ptr(), None, out.data_ptr(), out.stride(0), int(idx.numel()), x.shape[1],
-                                             _dtype_code(x), None)
-    _lib.check(code, "dgll_hip_gather_rows")
+        out = alloc_features(idx.numel(), x.shape[1], x.dtype, dev, pad_to=16 // x.element_size())
+    _lib.launch("dgll_hip_gather_rows", dev, None, 0, x.data_ptr(), x.stride(0), idx.data_ptr(), None, out.data_ptr(), out.stride(0),
+                int(idx.numel()), x.shape[1], _dtype_code(x), None)
     return out

@@ -9,6 +9,7 @@ Other dtypes / shapes / devices fall back to torch (fp32 CPU parity paths, short
 import torch
 
 from . import _lib
+from .ops import alloc_features, as_rows16, pitch16_ok, rows16_ok
 
 _SLABS = 256
 _GW_MIN_ROWS = 256       # rows per slab of the split-K weight gradient below which no further slabs are made (tools/gradw_short_probe.py:
@@ -37,11 +38,8 @@ def _pack_now(wt, rows=None):
     if wt.is_cuda and wt.dtype in (torch.float32, torch.bfloat16):
         wt = wt.detach()
         out = torch.empty((rows, ld), dtype=torch.bfloat16, device=wt.device)
-        with _lib.on_device(wt.device):
-            code = _lib.lib.dgll_hip_pack_weight_bf16(_lib.raw_stream(wt.device), wt.data_ptr(),
-                                                      _lib.F32 if wt.dtype == torch.float32 else _lib.BF16, wt.stride(0), wt.stride(1),
-                                                      n, k, out.data_ptr(), ld, rows)
-        _lib.check(code, "dgll_hip_pack_weight_bf16")
+        _lib.launch("dgll_hip_pack_weight_bf16", wt.device, wt.data_ptr(), _lib.F32 if wt.dtype == torch.float32 else _lib.BF16,
+                    wt.stride(0), wt.stride(1), n, k, out.data_ptr(), ld, rows)
         return out
     out = torch.zeros((rows, ld), dtype=torch.bfloat16, device=wt.device)
     out[:n, :k] = wt
@@ -56,17 +54,8 @@ def wcast(w, like):
     return w.to(like.dtype)
 
 
-def _timed(tag, device):
-    """HIP-event bracket of one launch for bench.py's tables (ops.LaunchTimer); None when no timer is active."""
-    from . import ops
-
-    timer = ops.LaunchTimer.active
-    return timer.start(tag, device) if timer is not None else None
-
-
 def _mfma_ok(*mats):
-    return all(m is None or (m.is_cuda and m.dtype == torch.bfloat16 and m.dim() == 2 and m.stride(1) == 1
-                             and m.stride(0) % 8 == 0 and m.data_ptr() % 16 == 0) for m in mats)
+    return all(m is None or (m.is_cuda and m.dtype == torch.bfloat16 and m.dim() == 2 and pitch16_ok(m)) for m in mats)
 
 
 def bit_words(n):
@@ -100,55 +89,34 @@ def transform_bf16(a1, wt1, a2=None, wt2=None, relu=False, out_dtype=torch.bfloa
     p2 = _pad_wt(wt2) if a2 is not None else None
     own_store = out is None       # `out`: a caller's [M, N] buffer (rows of a larger matrix, say); its padding is not ours to write
     if own_store:
-        ld_align = ld_align or (8 if out_dtype == torch.bfloat16 else 4)
-        ld = -(-n // ld_align) * ld_align
-        store = torch.empty((m, ld), dtype=out_dtype, device=a1.device)
-        out = store[:, :n] if ld != n else store
+        out = alloc_features(m, n, out_dtype, a1.device, pad_to=ld_align or (8 if out_dtype == torch.bfloat16 else 4))
     elif out.shape != (m, n) or out.dtype != out_dtype or out.stride(1) != 1 or not out.is_cuda:
         raise ValueError("transform_bf16: `out` must be a [M, N] device tensor of the output dtype with contiguous rows")
     if bias is not None:
         bias = bias.detach().float().contiguous()
-    with _lib.on_device(a1.device):
-        if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.shape != (m,) or not row_scale.is_contiguous()):
-            raise ValueError("row_scale must be a contiguous fp32 vector with one entry per row")
-        if out_gate is not None and (out_gate.dtype != torch.bfloat16 or out_gate.shape != (m, n) or out_gate.stride(1) != 1):
-            raise ValueError("out_gate must be bf16 [M, N] with contiguous rows")
-        if addend is not None and (addend.dtype != torch.bfloat16 or addend.shape != (m, n) or addend.stride(1) != 1):
-            raise ValueError("addend must be bf16 [M, N] with contiguous rows")
-        end = _timed(("transform", m, a1.shape[1], a2.shape[1] if a2 is not None else 0, n,
-                      "+".join(t for t, on in (("gate", out_gate is not None and gate_bits is None), ("gatebits", gate_bits is not None),
-                                               ("signbits", bits_out), ("addend", addend is not None),
-                                               ("row_scale", row_scale is not None), ("mask", mask is not None)) if on)), a1.device)
-        bits = torch.empty((m, bit_words(n)), dtype=torch.int32, device=a1.device) if bits_out else None
-        if bits is not None or gate_bits is not None:
-            code = _lib.lib.dgll_hip_transform_bf16_bits(
-                _lib.raw_stream(a1.device), a1.data_ptr(), a1.stride(0), a1.shape[1], p1.data_ptr(),
-                p1.stride(0), a2.data_ptr() if a2 is not None else None, a2.stride(0) if a2 is not None else 0,
-                a2.shape[1] if a2 is not None else 0, p2.data_ptr() if p2 is not None else None,
-                p2.stride(0) if p2 is not None else 0, p1.shape[0], out.data_ptr(), out.stride(0), m, n,
-                int(relu) | (2 if own_store else 0), bias.data_ptr() if bias is not None else None,
-                out_gate.data_ptr() if out_gate is not None else None, out_gate.stride(0) if out_gate is not None else 0,
-                gate_bits.data_ptr() if gate_bits is not None else None, gate_bits.stride(0) if gate_bits is not None else 0,
-                bits.data_ptr() if bits is not None else None, bits.stride(0) if bits is not None else 0)
-            if end is not None:
-                end.record(torch.cuda.current_stream(a1.device))
-            _lib.check(code, "dgll_hip_transform_bf16_bits")
-            return (out, bits) if bits_out else out
-        code = _lib.lib.dgll_hip_transform_bf16_add(
-            _lib.raw_stream(a1.device), a1.data_ptr(), a1.stride(0), a1.shape[1], p1.data_ptr(),
-            p1.stride(0), a2.data_ptr() if a2 is not None else None, a2.stride(0) if a2 is not None else 0,
-            a2.shape[1] if a2 is not None else 0, p2.data_ptr() if p2 is not None else None,
-            p2.stride(0) if p2 is not None else 0, p1.shape[0], mask.data_ptr() if mask is not None else None,
-            mask.stride(0) if mask is not None else 0, out.data_ptr(), out.stride(0),
-            _lib.BF16 if out_dtype == torch.bfloat16 else _lib.F32, m, n,
-            int(relu) | (2 if own_store else 0),     # bit 1: `store` is this function's own allocation: its row padding may be written
-            bias.data_ptr() if bias is not None else None,
-            out_gate.data_ptr() if out_gate is not None else None, out_gate.stride(0) if out_gate is not None else 0,
-            row_scale.data_ptr() if row_scale is not None else None,
-            addend.data_ptr() if addend is not None else None, addend.stride(0) if addend is not None else 0)
-        if end is not None:
-            end.record(torch.cuda.current_stream(a1.device))
-    _lib.check(code, "dgll_hip_transform_bf16")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.shape != (m,) or not row_scale.is_contiguous()):
+        raise ValueError("row_scale must be a contiguous fp32 vector with one entry per row")
+    if out_gate is not None and (out_gate.dtype != torch.bfloat16 or out_gate.shape != (m, n) or out_gate.stride(1) != 1):
+        raise ValueError("out_gate must be bf16 [M, N] with contiguous rows")
+    if addend is not None and (addend.dtype != torch.bfloat16 or addend.shape != (m, n) or addend.stride(1) != 1):
+        raise ValueError("addend must be bf16 [M, N] with contiguous rows")
+    k2 = a2.shape[1] if a2 is not None else 0
+    tag = ("transform", m, a1.shape[1], k2, n,
+           "+".join(t for t, on in (("gate", out_gate is not None and gate_bits is None), ("gatebits", gate_bits is not None),
+                                    ("signbits", bits_out), ("addend", addend is not None),
+                                    ("row_scale", row_scale is not None), ("mask", mask is not None)) if on))
+    operands = (a1.data_ptr(), a1.stride(0), a1.shape[1], p1.data_ptr(), p1.stride(0), _lib.ptr(a2), _lib.pitch(a2), k2,
+                _lib.ptr(p2), _lib.pitch(p2), p1.shape[0])
+    flags = int(relu) | (2 if own_store else 0)      # bit 1: `out` is this function's own allocation: its row padding may be written
+    bits = torch.empty((m, bit_words(n)), dtype=torch.int32, device=a1.device) if bits_out else None
+    if bits is not None or gate_bits is not None:
+        _lib.launch("dgll_hip_transform_bf16_bits", a1.device, *operands, out.data_ptr(), out.stride(0), m, n, flags, _lib.ptr(bias),
+                    _lib.ptr(out_gate), _lib.pitch(out_gate), _lib.ptr(gate_bits), _lib.pitch(gate_bits), _lib.ptr(bits), _lib.pitch(bits),
+                    tag=tag)
+        return (out, bits) if bits_out else out
+    _lib.launch("dgll_hip_transform_bf16_add", a1.device, *operands, _lib.ptr(mask), _lib.pitch(mask), out.data_ptr(), out.stride(0),
+                _lib.BF16 if out_dtype == torch.bfloat16 else _lib.F32, m, n, flags, _lib.ptr(bias), _lib.ptr(out_gate),
+                _lib.pitch(out_gate), _lib.ptr(row_scale), _lib.ptr(addend), _lib.pitch(addend), tag=tag)
     return out
 
 
@@ -166,20 +134,13 @@ def transform_bf16_cat(a, wt_first, wt_second):
     rows, ld = 2 * hp, -(-k // 64) * 64
     packed = torch.empty((rows, ld), dtype=torch.bfloat16, device=a.device)
     store = torch.empty((m, rows), dtype=torch.bfloat16, device=a.device)
-    with _lib.on_device(a.device):
-        stream = _lib.raw_stream(a.device)
-        for i, wt in enumerate((wt_first, wt_second)):           # cast, zero padding and layout of each half: one small launch
-            w = wt.detach()
-            code = _lib.lib.dgll_hip_pack_weight_bf16(stream, w.data_ptr(), _lib.F32 if w.dtype == torch.float32 else _lib.BF16,
-                                                      w.stride(0), w.stride(1), n, k, packed.data_ptr() + i * hp * ld * 2, ld, hp)
-            _lib.check(code, "dgll_hip_pack_weight_bf16")
-        end = _timed(("transform", m, k, 0, hp + n, "two products"), a.device)
-        code = _lib.lib.dgll_hip_transform_bf16(
-            stream, a.data_ptr(), a.stride(0), k, packed.data_ptr(), ld, None, 0, 0, None, 0, rows, None, 0,
-            store.data_ptr(), rows, _lib.BF16, m, hp + n, 2, None)          # relu bit 1: the row padding is ours (zeros)
-        if end is not None:
-            end.record(torch.cuda.current_stream(a.device))
-    _lib.check(code, "dgll_hip_transform_bf16")
+    for i, wt in enumerate((wt_first, wt_second)):           # cast, zero padding and layout of each half: one small launch
+        w = wt.detach()
+        _lib.launch("dgll_hip_pack_weight_bf16", a.device, w.data_ptr(), _lib.F32 if w.dtype == torch.float32 else _lib.BF16,
+                    w.stride(0), w.stride(1), n, k, packed.data_ptr() + i * hp * ld * 2, ld, hp)
+    _lib.launch("dgll_hip_transform_bf16", a.device, a.data_ptr(), a.stride(0), k, packed.data_ptr(), ld, None, 0, 0, None, 0, rows,
+                None, 0, store.data_ptr(), rows, _lib.BF16, m, hp + n, 2, None,          # relu bit 1: the row padding is ours (zeros)
+                tag=("transform", m, k, 0, hp + n, "two products"))
     return store[:, :n], store[:, hp:hp + n]
 
 
@@ -195,8 +156,6 @@ def sage_fused_forward(graph, x, reduce, h_self, wt_self, wt_nbr, relu, bias=Non
     32-row tile into LDS and feeds it to the MFMAs (dgll_hip_sage_fused_forward).  wt_*: [N, K] (transposed weights, any float
     dtype); wt_nbr None: the aggregate is added instead of transformed (x.shape[1] == N).  agg: the aggregated rows
     [n_rows, feat] bf16 when keep_agg (the weight gradient needs them), else None."""
-    from . import ops
-
     dev = x.device
     feat = x.shape[1]
     n = wt_nbr.shape[0] if wt_nbr is not None else (wt_self.shape[0] if wt_self is not None else feat)
@@ -205,35 +164,22 @@ def sage_fused_forward(graph, x, reduce, h_self, wt_self, wt_nbr, relu, bias=Non
     w_rows = (p1 if p1 is not None else p2).shape[0]
     if p1 is not None and p2 is not None and p1.shape[0] != p2.shape[0]:
         raise ValueError("both weight matrices must have N rows")
-    ld_align = ld_align or 8
-    ld = -(-n // ld_align) * ld_align
-    store = torch.empty((graph.n_rows, ld), dtype=torch.bfloat16, device=dev)
-    out = store[:, :n] if ld != n else store
+    out = alloc_features(graph.n_rows, n, torch.bfloat16, dev, pad_to=ld_align or 8)
     plan = graph.plan()
     long_rows = graph.num_long_rows() > 0
     agg = None
     if keep_agg or long_rows:
-        agg = ops.alloc_features(graph.n_rows, feat, torch.bfloat16, dev)
+        agg = alloc_features(graph.n_rows, feat, torch.bfloat16, dev)
     ws_bytes = graph.workspace_bytes(feat) if long_rows else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     if bias is not None:
         bias = bias.detach().float().contiguous()
-    val = graph.val
-    with torch.cuda.device(dev):
-        end = _timed(("fused_sage", graph.n_rows, feat, h_self.shape[1] if h_self is not None else 0, n, graph.nnz), dev)
-        code = _lib.lib.dgll_hip_sage_fused_forward(
-            torch.cuda.current_stream(dev).cuda_stream, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(),
-            val.data_ptr() if val is not None else None, x.data_ptr(), x.stride(0), feat,
-            _lib.REDUCE_MEAN if reduce == "mean" else _lib.REDUCE_SUM,
-            h_self.data_ptr() if h_self is not None else None, h_self.stride(0) if h_self is not None else 0,
-            h_self.shape[1] if h_self is not None else 0, p1.data_ptr() if p1 is not None else None,
-            p1.stride(0) if p1 is not None else 0, p2.data_ptr() if p2 is not None else None, p2.stride(0) if p2 is not None else 0,
-            w_rows, bias.data_ptr() if bias is not None else None, int(relu), out.data_ptr(), out.stride(0), n,
-            agg.data_ptr() if agg is not None else None, agg.stride(0) if agg is not None else 0, graph.n_rows, graph.n_cols,
-            ws.data_ptr() if ws is not None else None, ws_bytes)
-        if end is not None:
-            end.record(torch.cuda.current_stream(dev))
-    _lib.check(code, "dgll_hip_sage_fused_forward")
+    k_self = h_self.shape[1] if h_self is not None else 0
+    _lib.launch("dgll_hip_sage_fused_forward", dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(graph.val),
+                x.data_ptr(), x.stride(0), feat, _lib.REDUCE_MEAN if reduce == "mean" else _lib.REDUCE_SUM,
+                _lib.ptr(h_self), _lib.pitch(h_self), k_self, _lib.ptr(p1), _lib.pitch(p1), _lib.ptr(p2), _lib.pitch(p2), w_rows,
+                _lib.ptr(bias), int(relu), out.data_ptr(), out.stride(0), n, _lib.ptr(agg), _lib.pitch(agg), graph.n_rows, graph.n_cols,
+                _lib.ptr(ws), ws_bytes, tag=("fused_sage", graph.n_rows, feat, k_self, n, graph.nnz))
     return out, (agg if keep_agg else None)
 
 
@@ -244,27 +190,15 @@ def transform_bf16_dual(a, wt1, wt2, out1=None):
     if wt2.shape != wt1.shape or n > 256 or a.shape[1] > 256:
         raise ValueError("transform_bf16_dual: two [N <= 256, K <= 256] weight matrices of one shape")
     p1, p2 = _pad_wt(wt1, rows=256), _pad_wt(wt2, rows=256)
-    ld = -(-n // 8) * 8
-    outs = [torch.empty((m, ld), dtype=torch.bfloat16, device=a.device) for _ in range(2)]
-    o1, o2 = (o[:, :n] if ld != n else o for o in outs)
+    o1, o2 = (alloc_features(m, n, torch.bfloat16, a.device) for _ in range(2))
     if out1 is not None:       # the first product into a caller's rows (a range of a row_slices gradient buffer): bf16, 16-byte pitch
         if out1.shape != (m, n) or out1.dtype != torch.bfloat16 or out1.stride(1) != 1 or out1.stride(0) % 8 or out1.data_ptr() % 16:
             raise ValueError("transform_bf16_dual(out1=): [M, N] bf16 rows on a 16-byte pitch")
         o1 = out1
-    with _lib.on_device(a.device):
-        end = _timed(("transform_dual", m, a.shape[1], 0, 2 * n, ""), a.device)
-        code = _lib.lib.dgll_hip_transform_bf16_dual(
-            _lib.raw_stream(a.device), a.data_ptr(), a.stride(0), a.shape[1], p1.data_ptr(), p2.data_ptr(),
-            p1.stride(0), p1.shape[0], o1.data_ptr(), o1.stride(0), o2.data_ptr(), o2.stride(0), m, n)
-        if end is not None:
-            end.record(torch.cuda.current_stream(a.device))
-    _lib.check(code, "dgll_hip_transform_bf16_dual")
+    _lib.launch("dgll_hip_transform_bf16_dual", a.device, a.data_ptr(), a.stride(0), a.shape[1], p1.data_ptr(), p2.data_ptr(),
+                p1.stride(0), p1.shape[0], o1.data_ptr(), o1.stride(0), o2.data_ptr(), o2.stride(0), m, n,
+                tag=("transform_dual", m, a.shape[1], 0, 2 * n, ""))
     return o1, o2
-
-
-def _rows16_ok(x):
-    epv = 16 // x.element_size()
-    return x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % epv == 0 and x.data_ptr() % 16 == 0
 
 
 def _relu_backward_rows(g, out):
@@ -272,7 +206,7 @@ def _relu_backward_rows(g, out):
     boundaries (the loss's: 41 classes on a 128-byte pitch) keeps that layout -- the masked copy is written into a buffer of the same
     pitch, so the products that follow read it as it is; made dense first (`.contiguous()`) its 82-byte rows were re-laid out four times
     (twice for the input gradients, twice for the weight gradients: five tiny launches per mini-batch step)."""
-    if g.dim() == 2 and g.stride(1) == 1 and not g.is_contiguous() and _rows16_ok(g):
+    if g.dim() == 2 and g.stride(1) == 1 and not g.is_contiguous() and rows16_ok(g):
         buf = torch.empty((g.shape[0], g.stride(0)), dtype=g.dtype, device=g.device)
         gm = buf[:, :g.shape[1]]
         torch.ops.aten.threshold_backward.grad_input(g, out, 0, grad_input=gm)
@@ -280,16 +214,7 @@ def _relu_backward_rows(g, out):
     return torch.ops.aten.threshold_backward(g.contiguous(), out, 0)
 
 
-def _as_rows16(x):
-    """x with unit column stride and 16-byte aligned rows: itself when it already is, else one copy into a padded buffer."""
-    epv = 16 // x.element_size()
-    if (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % epv == 0 and x.data_ptr() % 16 == 0):
-        return x
-    ld = -(-x.shape[1] // epv) * epv
-    buf = torch.empty((x.shape[0], ld), dtype=x.dtype, device=x.device)
-    out = buf[:, :x.shape[1]] if ld != x.shape[1] else buf
-    out.copy_(x)
-    return out
+_as_rows16 = as_rows16      # the tests and tools reach it under this name
 
 
 def _mm_f32(a, wt, relu, bias, addend, a2=None, wt2=None, gate=None):
@@ -307,6 +232,8 @@ def _mm_f32(a, wt, relu, bias, addend, a2=None, wt2=None, gate=None):
         wt2 = wt2.to(torch.float32)
         wt2 = wt2 if wt2.stride(1) == 1 else wt2.contiguous()
         k2 = a2.shape[1]
+    else:
+        wt2 = None
     out = torch.empty((m, n), dtype=torch.float32, device=a.device)
     if addend is not None:
         addend = addend.to(torch.float32)
@@ -316,23 +243,22 @@ def _mm_f32(a, wt, relu, bias, addend, a2=None, wt2=None, gate=None):
         gate = gate if gate.stride(1) == 1 else gate.contiguous()
     if bias is not None:
         bias = bias.detach().to(torch.float32).contiguous()
-    with _lib.on_device(a.device):
-        stream = _lib.raw_stream(a.device)
-        end = _timed(("transform_f32", m, k, k2, n, "+".join(t for t, on in (("gate", gate is not None), ("addend", addend is not None)) if on)),
-                     a.device)
-        for n0 in range(0, n, 256):
-            nn = min(256, n - n0)
-            code = _lib.lib.dgll_hip_mm2_f32(
-                stream, a.data_ptr(), a.stride(0), wt.data_ptr() + n0 * wt.stride(0) * 4, wt.stride(0), k,
-                a2.data_ptr() if a2 is not None else None, a2.stride(0) if a2 is not None else 0,
-                wt2.data_ptr() + n0 * wt2.stride(0) * 4 if a2 is not None else None, wt2.stride(0) if a2 is not None else 0, k2,
-                out.data_ptr() + n0 * 4, out.stride(0), m, nn,
-                bias.data_ptr() + n0 * 4 if bias is not None else None, int(relu),
-                addend.data_ptr() + n0 * 4 if addend is not None else None, addend.stride(0) if addend is not None else 0,
-                gate.data_ptr() + n0 * 4 if gate is not None else None, gate.stride(0) if gate is not None else 0)
-            _lib.check(code, "dgll_hip_mm2_f32")
-        if end is not None:
-            end.record(torch.cuda.current_stream(a.device))
+    timer = _lib.LaunchTimer.active      # ONE bracket over the 256-column launches: opened and closed here, not by `launch`
+    if timer is not None:
+        on = torch.cuda.current_stream(a.device)
+        end = timer.start(("transform_f32", m, k, k2, n, "+".join(t for t, has in (("gate", gate is not None), ("addend", addend is not None)) if has)),
+                          on)
+
+    def at(t, n0, step=4):      # address of column n0 of an optional fp32 operand (step = 4 * pitch: of row n0)
+        return None if t is None else t.data_ptr() + n0 * step
+
+    for n0 in range(0, n, 256):
+        _lib.launch("dgll_hip_mm2_f32", a.device, a.data_ptr(), a.stride(0), at(wt, n0, 4 * wt.stride(0)), wt.stride(0), k,
+                    _lib.ptr(a2), _lib.pitch(a2), at(wt2, n0, 4 * _lib.pitch(wt2)), _lib.pitch(wt2), k2,
+                    at(out, n0), out.stride(0), m, min(256, n - n0), at(bias, n0), int(relu), at(addend, n0), _lib.pitch(addend),
+                    at(gate, n0), _lib.pitch(gate))
+    if timer is not None:
+        end.record(on)
     return out
 
 
@@ -351,7 +277,7 @@ def mm_nt(a, wt, relu=False, bias=None, addend=None, out=None):
         return _mm_f32(a, wt, relu, bias, addend)
     if a.dtype != torch.bfloat16:
         raise TypeError("dgll_amd dense products take float32 or bfloat16 matrices, got %s" % a.dtype)
-    a = _as_rows16(a)
+    a = as_rows16(a)
     if addend is not None:
         addend = addend.to(torch.bfloat16)
         addend = addend if addend.stride(1) == 1 else addend.contiguous()
@@ -374,7 +300,7 @@ def mm2_nt(a1, wt1, a2, wt2, relu=False, gate=None):
     if not (a1.is_cuda and a1.dtype == torch.bfloat16 and a2.dtype == torch.bfloat16):
         res = mm_nt(a2, wt2, relu=relu, addend=mm_nt(a1, wt1))      # mixed / host: the addend stays fp32 (exact); host: torch
         return res if gate is None else torch.ops.aten.threshold_backward(res, gate.to(res.dtype), 0)
-    a1, a2 = _as_rows16(a1), _as_rows16(a2)
+    a1, a2 = as_rows16(a1), as_rows16(a2)
     n = wt1.shape[0]
     parts = [transform_bf16(a1, wt1[n0:n0 + 256], a2, wt2[n0:n0 + 256], relu=relu) for n0 in range(0, n, 256)]
     res = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
@@ -414,8 +340,7 @@ _GW_WORKSPACE = {}
 
 
 def _gradw_ok(*mats):
-    return all(m is not None and m.is_cuda and m.dtype == torch.bfloat16 and m.dim() == 2 and m.stride(1) == 1
-               and m.stride(0) % 8 == 0 and m.data_ptr() % 16 == 0 and m.shape[1] <= 256 for m in mats)
+    return all(m is not None and _mfma_ok(m) and m.shape[1] <= 256 for m in mats)
 
 
 def _out_ok(out, k, n, device):
@@ -433,7 +358,7 @@ def _grad_weight_hip(x1, x2, g, out1=None, out2=None, transposed=False):
     n_cu = torch.cuda.get_device_properties(g.device).multi_processor_count
     slabs = max(1, min(4096, n_cu // types, -(-m // _GW_MIN_ROWS)))   # at least _GW_MIN_ROWS rows per slab: short operands (sampled
                                                                        # blocks) would otherwise pay for summing hundreds of near-empty partials
-    ld_max = max(x1.stride(0), x2.stride(0) if x2 is not None else 0, g.stride(0))
+    ld_max = max(x1.stride(0), _lib.pitch(x2), g.stride(0))
 
     def slab_fits(sl):      # the kernel's own check (gradw.hip): rows per slab rounded up to 64, + 256 rows of prefetch overshoot, in uint32 bytes
         per = max(64, -(-(-(-m // sl)) // 64) * 64)
@@ -453,17 +378,10 @@ def _grad_weight_hip(x1, x2, g, out1=None, out2=None, transposed=False):
     s1, s2 = ((n, k1), (n, k2)) if transposed else ((k1, n), (k2, n))
     d1 = out1 if _out_ok(out1, s1[0], s1[1], g.device) else torch.empty(s1, dtype=torch.float32, device=g.device)
     d2 = (out2 if _out_ok(out2, s2[0], s2[1], g.device) else torch.empty(s2, dtype=torch.float32, device=g.device)) if x2 is not None else None
-    entry = "dgll_hip_grad_weight_bf16_tr" if transposed else "dgll_hip_grad_weight_bf16"
-    with _lib.on_device(g.device):       # the launch (and its event bracket) belong to g's device, whatever is current
-        end = _timed(("grad_weight", m, k1, k2, n, "tr" if transposed else ""), g.device)
-        code = getattr(_lib.lib, entry)(
-            _lib.raw_stream(g.device), x1.data_ptr(), x1.stride(0), k1,
-            x2.data_ptr() if x2 is not None else None, x2.stride(0) if x2 is not None else 0, k2, g.data_ptr(), g.stride(0), n, m,
-            ws.data_ptr(), ws.numel() * 4, slabs, d1.data_ptr(), d1.stride(0), d2.data_ptr() if d2 is not None else None,
-            d2.stride(0) if d2 is not None else 0)
-        if end is not None:
-            end.record(torch.cuda.current_stream(g.device))
-    _lib.check(code, entry)
+    # (the launch and its event bracket belong to g's device, whatever is current)
+    _lib.launch("dgll_hip_grad_weight_bf16_tr" if transposed else "dgll_hip_grad_weight_bf16", g.device, x1.data_ptr(), x1.stride(0), k1,
+                _lib.ptr(x2), _lib.pitch(x2), k2, g.data_ptr(), g.stride(0), n, m, ws.data_ptr(), ws.numel() * 4, slabs,
+                d1.data_ptr(), d1.stride(0), _lib.ptr(d2), _lib.pitch(d2), tag=("grad_weight", m, k1, k2, n, "tr" if transposed else ""))
     return d1, d2
 
 
@@ -484,14 +402,8 @@ def _grad_weight_f32(x, g):
     need = int(_lib.lib.dgll_hip_grad_weight_f32_workspace(k, n, slabs))
     ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
     out = torch.empty((k, n), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        end = _timed(("grad_weight_f32", m, k, 0, n, ""), x.device)
-        code = _lib.lib.dgll_hip_grad_weight_f32(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), x.stride(0),
-                                                 g.data_ptr(), g.stride(0), out.data_ptr(), out.stride(0), m, k, n, ws.data_ptr(),
-                                                 need, slabs)
-        if end is not None:
-            end.record(torch.cuda.current_stream(x.device))
-    _lib.check(code, "dgll_hip_grad_weight_f32")
+    _lib.launch("dgll_hip_grad_weight_f32", x.device, x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0), out.data_ptr(), out.stride(0),
+                m, k, n, ws.data_ptr(), need, slabs, tag=("grad_weight_f32", m, k, 0, n, ""))
     return out
 
 
@@ -512,7 +424,7 @@ def grad_weight(x, g, out=None):
         return _into(out, torch.mm(x.t(), g.to(x.dtype)).float())
     if x.dtype == torch.float32 or g.dtype == torch.float32:
         return _into(out, _grad_weight_f32(x, g))
-    x, g = _as_rows16(x), _as_rows16(g.to(x.dtype))
+    x, g = as_rows16(x), as_rows16(g.to(x.dtype))
     k, n = x.shape[1], g.shape[1]
     if k <= 256 and n <= 256:
         return _grad_weight_hip(x, None, g, out1=out)[0]
@@ -542,7 +454,7 @@ def grad_weight_pair(x1, x2, g, out1=None, out2=None):
     wide = (x1.is_cuda and x1.dtype == x2.dtype == g.dtype == torch.bfloat16 and g.shape[1] <= 256 and _gradw_ok(g)
             and max(x1.shape[1], x2.shape[1]) > 256)
     if wide:
-        x1, x2 = _as_rows16(x1), _as_rows16(x2)
+        x1, x2 = as_rows16(x1), as_rows16(x2)
         n = g.shape[1]
         outs = [o if _out_ok(o, x.shape[1], n, g.device) and o.is_contiguous() else torch.empty((x.shape[1], n), dtype=torch.float32, device=g.device)
                 for o, x in ((out1, x1), (out2, x2))]
@@ -606,7 +518,7 @@ class _SageTransform(torch.autograd.Function):
         h, agg, wsd, wnd, out = ctx.saved_tensors
         if ctx.relu:
             g = _relu_backward_rows(g, out)   # one vectorised pass: g where out > 0
-        elif not (g.stride(1) == 1 and _rows16_ok(g)):
+        elif not (g.stride(1) == 1 and rows16_ok(g)):
             g = g.contiguous()
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
             # the self path's product straight into its rows of the stacked input's gradient buffer (no copy pass afterwards)

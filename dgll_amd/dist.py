@@ -851,7 +851,7 @@ class _DistSageLayerOnAll(torch.autograd.Function):
         # halo rows (which have no self path here: their owner adds it).  Replaces (g.Wn^T)/deg, g.Ws^T, an accumulating gated SpMM
         # over local^T and a gated SpMM over halo^T.
         agg_first = (fused_layers.BACKWARD_ORDER != "transform-first" and ctx.needs_input_grad[0] and engine._spmm_fn is None
-                     and g.is_cuda and dense._mfma_ok(g) and fused_layers._aligned(g) and wsd.shape[1] <= wsd.shape[0] <= 256
+                     and g.is_cuda and dense._mfma_ok(g) and ops.pitch16_ok(g) and wsd.shape[1] <= wsd.shape[0] <= 256
                      and p.merged is not None and (not ctx.gate_input or h_all.stride(1) == 1))
         if agg_first:
             # two launches, one per column half of A: the halo half's rows are short (a remote node feeds ~3 of this rank's rows) and take

@@ -60,10 +60,8 @@ def sgns_negatives(walks, window, negatives, noise, seed, first_walk_index=0):
     out = torch.empty((n, L, 2 * W, K), dtype=torch.int32, device=walks.device)
     if out.numel() == 0:
         return out
-    with _lib.on_device(walks.device):
-        _lib.check(_lib.lib.dgll_hip_sgns_negatives(_lib.raw_stream(walks.device), walks.data_ptr(), n, L, W, K, noise.cdf.data_ptr(), noise.n,
-                                                    int(first_walk_index) & _MASK, int(seed) & _MASK, out.data_ptr()),
-                   "dgll_hip_sgns_negatives")
+    _lib.launch("dgll_hip_sgns_negatives", walks.device, walks.data_ptr(), n, L, W, K, noise.cdf.data_ptr(), noise.n,
+                int(first_walk_index) & _MASK, int(seed) & _MASK, out.data_ptr())
     return out
 
 
@@ -90,8 +88,6 @@ def sgns_step(W_in, W_out, walks, window, negatives, noise, lr, seed, first_walk
     g = torch.empty(slots, dtype=torch.float32, device=dev)
     tgt = torch.empty(slots, dtype=torch.int32, device=dev)
     delta = torch.empty(n * L * D, dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib.dgll_hip_sgns_step(_lib.raw_stream(dev), W_in.data_ptr(), W_out.data_ptr(), N, D, walks.data_ptr(), n, L, W, K,
-                                               noise.cdf.data_ptr(), int(first_walk_index) & _MASK, int(seed) & _MASK, float(lr),
-                                               g.data_ptr(), tgt.data_ptr(), delta.data_ptr(), loss.data_ptr()), "dgll_hip_sgns_step")
+    _lib.launch("dgll_hip_sgns_step", dev, W_in.data_ptr(), W_out.data_ptr(), N, D, walks.data_ptr(), n, L, W, K, noise.cdf.data_ptr(),
+                int(first_walk_index) & _MASK, int(seed) & _MASK, float(lr), g.data_ptr(), tgt.data_ptr(), delta.data_ptr(), loss.data_ptr())
     return loss

@@ -61,11 +61,9 @@ def random_walks(g, starts, length, p=1.0, q=1.0, seed=0, first_walk_index=0, st
     walks = torch.empty((n, length), dtype=torch.int32, device=starts.device)
     if info is None:
         info = torch.zeros(2, dtype=torch.int64, device=starts.device)
-    with _lib.on_device(starts.device):
-        st = _lib.raw_stream(starts.device) if stream is None else stream.cuda_stream
-        _lib.check(_lib.lib.dgll_hip_random_walk(st, g.rowptr.data_ptr(), g.col.data_ptr(), g.n_rows, starts.data_ptr(), n, length,
-                                                 int(first_walk_index) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, p, q,
-                                                 MAX_ATTEMPTS, walks.data_ptr(), info.data_ptr()), "dgll_hip_random_walk")
+    _lib.launch("dgll_hip_random_walk", starts.device, g.rowptr.data_ptr(), g.col.data_ptr(), g.n_rows, starts.data_ptr(), n, length,
+                int(first_walk_index) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, p, q, MAX_ATTEMPTS, walks.data_ptr(),
+                info.data_ptr(), stream=stream)
     return walks
 
 

@@ -31,12 +31,8 @@ def gcn_fused_forward(row_ptr, col_idx, values, X, W, num_neighbors, actual_F):
     H = torch.zeros((N, H_dim), dtype=torch.float32, device=X.device)            # gcn_extension.cpp:43-44
     ws_bytes = int(_lib.lib.dgll_hip_gcn_fused_workspace_bytes(N, int(actual_F), H_dim))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
-    with torch.cuda.device(X.device):
-        code = _lib.lib.dgll_hip_gcn_fused_forward(
-            torch.cuda.current_stream(X.device).cuda_stream, row_ptr.data_ptr(), col_idx.data_ptr(), values.data_ptr(),
-            X.data_ptr(), W.data_ptr(), H.data_ptr(), N, F_padded, int(actual_F), H_dim, int(col_idx.numel()),
-            ws.data_ptr(), ws_bytes)
-    _lib.check(code, "dgll_hip_gcn_fused_forward")
+    _lib.launch("dgll_hip_gcn_fused_forward", X.device, row_ptr.data_ptr(), col_idx.data_ptr(), values.data_ptr(), X.data_ptr(),
+                W.data_ptr(), H.data_ptr(), N, F_padded, int(actual_F), H_dim, int(col_idx.numel()), ws.data_ptr(), ws_bytes)
     return H
 
 

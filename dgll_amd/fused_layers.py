@@ -54,10 +54,6 @@ def _bits_of(h):
     return bits
 
 
-def _aligned(t):
-    return (t.stride(0) * t.element_size()) % 16 == 0 and t.data_ptr() % 16 == 0 and t.stride(1) == 1
-
-
 class _SageGraphLayer(torch.autograd.Function):
     """out = act(h.Ws + reduce_A(h).Wn)  -- aggregate-then-transform (sageconv.py:33-41,72-75)."""
 
@@ -101,7 +97,7 @@ class _SageGraphLayer(torch.autograd.Function):
         gh = None
         f32 = g.is_cuda and g.dtype == torch.float32 and h.dtype == torch.float32      # the reference's own arithmetic (dgll/__init__.py:1)
         agg_first = (BACKWARD_ORDER != "transform-first" and ctx.needs_input_grad[0] and wsd.shape[1] <= wsd.shape[0]
-                     and (f32 or (dense._mfma_ok(g) and wsd.shape[0] <= 256 and _aligned(g)))
+                     and (f32 or (dense._mfma_ok(g) and wsd.shape[0] <= 256 and ops.pitch16_ok(g)))
                      and (not ctx.gate_input or h.stride(1) == 1))
         if agg_first:
             gt, _ = graph.transpose()
@@ -123,7 +119,7 @@ class _SageGraphLayer(torch.autograd.Function):
             if ctx.reduce == "mean":
                 scale = graph.mean_scale_transposed()
                 tval = scale if tval is None else tval * scale
-            if _aligned(gh) and _aligned(gagg):            # neighbour path lands on top of the self path in the epilogue
+            if ops.pitch16_ok(gh) and ops.pitch16_ok(gagg):            # neighbour path lands on top of the self path in the epilogue
                 gate = h if (ctx.gate_input and h.stride(1) == 1) else None
                 ops.spmm_raw(gt, gagg, val=tval, reduce="sum", out=gh, accumulate=True, gate=gate)
                 if ctx.gate_input and gate is None:

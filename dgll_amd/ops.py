@@ -34,42 +34,35 @@ def _row_major(x):
     return x
 
 
-def alloc_features(n_rows, feat, dtype, device, pad_to=8):
+def alloc_features(n_rows, feat, dtype, device, pad_to=8, zero_pad=False):
     """[n_rows, feat] view of a buffer whose leading dimension is padded to 16 bytes, so any feature width
-    takes the vectorised (global_load_dwordx4) path of the kernels."""
+    takes the vectorised (global_load_dwordx4) path of the kernels.  zero_pad: the padding columns hold zeros."""
     ld = (feat + pad_to - 1) // pad_to * pad_to
-    buf = torch.empty((n_rows, ld), dtype=dtype, device=device)
+    buf = (torch.zeros if zero_pad and ld != feat else torch.empty)((n_rows, ld), dtype=dtype, device=device)
     return buf[:, :feat] if ld != feat else buf
 
 
-class LaunchTimer:
-    """HIP-event timing of individual kernel launches on the stream they are issued on (bench.py's roofline leg).
-    Usage: `with LaunchTimer() as t: ...steps...` then t.summary() -> {tag: (count, avg_ms)}."""
-    active = None
+def pitch16_ok(x):
+    """Unit column stride, row pitch a whole number of 16-byte vectors, base pointer 16-byte aligned."""
+    return x.stride(1) == 1 and (x.stride(0) * x.element_size()) % 16 == 0 and x.data_ptr() % 16 == 0
 
-    def __init__(self):
-        self.records = []
 
-    def __enter__(self):
-        LaunchTimer.active = self
-        return self
+def rows16_ok(x):
+    """A matrix whose rows the kernels read as 16-byte vectors as it is: 2-D, non-overlapping rows on a 16-byte pitch."""
+    return x.dim() == 2 and x.stride(0) >= x.shape[1] and pitch16_ok(x)
 
-    def __exit__(self, *exc):
-        LaunchTimer.active = None
 
-    def start(self, tag, device):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(torch.cuda.current_stream(device))
-        self.records.append((tag, a, b))
-        return b
+def as_rows16(x, zero_pad=False):
+    """x itself when rows16_ok(x), else one copy into a padded buffer.  zero_pad: the copy's padding columns hold zeros (kernels
+    that load whole vectors and USE the columns behind the last one: SDDMM's dot product, the segment max)."""
+    if rows16_ok(x):
+        return x
+    out = alloc_features(x.shape[0], x.shape[1], x.dtype, x.device, pad_to=16 // x.element_size(), zero_pad=zero_pad)
+    out.copy_(x)
+    return out
 
-    def summary(self):
-        torch.cuda.synchronize()
-        out = {}
-        for tag, a, b in self.records:
-            n, tot = out.get(tag, (0, 0.0))
-            out[tag] = (n + 1, tot + a.elapsed_time(b))
-        return {k: (n, tot / n) for k, (n, tot) in out.items()}
+
+LaunchTimer = _lib.LaunchTimer      # bench.py and the tests reach it here
 
 
 def spmm_raw(graph, x, val=None, reduce="sum", bias=None, relu=False, out_dtype=None, out=None, row_scale=None,
@@ -100,27 +93,18 @@ def spmm_raw(graph, x, val=None, reduce="sum", bias=None, relu=False, out_dtype=
     plan = graph.plan()
     ws_bytes = graph.workspace_bytes(feat)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    timer = LaunchTimer.active
-    if timer is not None:      # what distinguishes the launch kinds of a step: width, dtype, weights, nnz, epilogue extras
+    if gate is not None and (gate.dtype != out.dtype or gate.shape != out.shape or gate.stride(1) != 1):
+        raise ValueError("gate must match the output's shape and dtype, rows contiguous")
+
+    def tag():      # what distinguishes the launch kinds of a step: width, dtype, weights, nnz, epilogue extras
         extra = "+".join(t for t, on in (("accumulate", bool(accumulate)), ("gate", gate is not None),
                                          ("row_scale", row_scale is not None)) if on)
-        end = timer.start(("spmm", feat, str(x.dtype), val is not None, graph.nnz, extra), x.device)
-    else:
-        end = None
-    with _lib.on_device(x.device):
-        stream = _lib.raw_stream(x.device)
-        if gate is not None and (gate.dtype != out.dtype or gate.shape != out.shape or gate.stride(1) != 1):
-            raise ValueError("gate must match the output's shape and dtype, rows contiguous")
-        code = _lib.lib.dgll_hip_spmm_csr_gated(
-            stream, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), val.data_ptr() if val is not None else None,
-            x.data_ptr(), x.stride(0), _dtype_code(x), out.data_ptr(), out.stride(0), _dtype_code(out),
-            graph.n_rows, graph.n_cols, feat, _REDUCE[reduce], epi, bias.data_ptr() if bias is not None else None,
-            ws.data_ptr() if ws is not None else None, ws_bytes,
-            row_scale.data_ptr() if row_scale is not None else None, 2 if accumulate in (2, "add") else int(bool(accumulate)),
-            gate.data_ptr() if gate is not None else None, gate.stride(0) if gate is not None else 0)
-    if end is not None:
-        end.record(torch.cuda.current_stream(x.device))
-    _lib.check(code, "dgll_hip_spmm_csr")
+        return "spmm", feat, str(x.dtype), val is not None, graph.nnz, extra
+
+    _lib.launch("dgll_hip_spmm_csr_gated", x.device, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(val),
+                x.data_ptr(), x.stride(0), _dtype_code(x), out.data_ptr(), out.stride(0), _dtype_code(out),
+                graph.n_rows, graph.n_cols, feat, _REDUCE[reduce], epi, _lib.ptr(bias), _lib.ptr(ws), ws_bytes,
+                _lib.ptr(row_scale), 2 if accumulate in (2, "add") else int(bool(accumulate)), _lib.ptr(gate), _lib.pitch(gate), tag=tag)
     return out
 
 
@@ -164,10 +148,9 @@ class _Spmm(torch.autograd.Function):
                 grad_x, acc = got
             else:
                 grad_x, acc = alloc_features(graph.n_cols, g.shape[1], g.dtype, g.device, pad_to=16 // g.element_size()), False
-            with _lib.on_device(g.device):
-                _lib.check(_lib.lib.dgll_hip_expand_rows(_lib.raw_stream(g.device), graph.rowptr.data_ptr(), graph.n_rows, g.data_ptr(), g.stride(0),
-                                                         grad_x.data_ptr(), grad_x.stride(0), graph.n_cols, g.shape[1], _dtype_code(g),
-                                                         1 if ctx.reduce == "mean" else 0, 1 if acc else 0), "dgll_hip_expand_rows")
+            _lib.launch("dgll_hip_expand_rows", g.device, graph.rowptr.data_ptr(), graph.n_rows, g.data_ptr(), g.stride(0),
+                        grad_x.data_ptr(), grad_x.stride(0), graph.n_cols, g.shape[1], _dtype_code(g),
+                        1 if ctx.reduce == "mean" else 0, 1 if acc else 0)
         elif ctx.needs_input_grad[0] and graph.identity_cols and graph.n_cols == graph.nnz:
             # the same through tensor ops (host tensors, weighted blocks): one gather,
             # no transposed CSR to sort together and no launch plan for it, both of which would be rebuilt every batch
@@ -375,22 +358,16 @@ class GateToken:
 
 def _xent_launch(z, target, soft, row_loss, grad, scale, mask_nonpositive=False, own_padding=False):
     n, c = z.shape
-    with _lib.on_device(z.device):
-        stream = _lib.raw_stream(z.device)
-        rl = row_loss.data_ptr() if row_loss is not None else None
-        gp, gld = (grad.data_ptr(), grad.stride(0)) if grad is not None else (None, 0)
-        sp = scale.data_ptr() if scale is not None else None
-        if mask_nonpositive or own_padding:      # own_padding: `grad` is a fresh padded allocation whose padding may be written (zeros)
-            code = _lib.lib.dgll_hip_softmax_xent_ex(stream, z.data_ptr(), z.stride(0), _dtype_code(z), None if soft else target.data_ptr(),
-                                                     target.data_ptr() if soft else None, target.stride(0) if soft else 0, rl, gp, gld,
-                                                     sp, n, c, (1 if mask_nonpositive else 0) | (2 if own_padding else 0))
-        elif soft:
-            code = _lib.lib.dgll_hip_softmax_xent_soft(stream, z.data_ptr(), z.stride(0), _dtype_code(z), target.data_ptr(),
-                                                       target.stride(0), rl, gp, gld, sp, n, c)
-        else:
-            code = _lib.lib.dgll_hip_softmax_xent(stream, z.data_ptr(), z.stride(0), _dtype_code(z), target.data_ptr(),
-                                                  rl, gp, gld, sp, n, c)
-    _lib.check(code, "dgll_hip_softmax_xent")
+    head = (z.data_ptr(), z.stride(0), _dtype_code(z))
+    tail = (_lib.ptr(row_loss), _lib.ptr(grad), _lib.pitch(grad), _lib.ptr(scale), n, c)
+    if mask_nonpositive or own_padding:      # own_padding: `grad` is a fresh padded allocation whose padding may be written (zeros)
+        _lib.launch("dgll_hip_softmax_xent_ex", z.device, *head, None if soft else target.data_ptr(),
+                    target.data_ptr() if soft else None, target.stride(0) if soft else 0, *tail,
+                    (1 if mask_nonpositive else 0) | (2 if own_padding else 0))
+    elif soft:
+        _lib.launch("dgll_hip_softmax_xent_soft", z.device, *head, target.data_ptr(), target.stride(0), *tail)
+    else:
+        _lib.launch("dgll_hip_softmax_xent", z.device, *head, target.data_ptr(), *tail)
 
 
 XENT_ONE_LAUNCH_ROWS = 1 << 16     # up to here the loss of a batch is finished by one workgroup (larger: the two-stage tree below)
@@ -427,9 +404,7 @@ class _CrossEntropy(torch.autograd.Function):
             row_loss = torch.empty(n, dtype=torch.float32, device=z.device)
             _xent_launch(z, target, soft, row_loss, None, None)
             res = torch.empty(4, dtype=torch.float32, device=z.device)
-            with _lib.on_device(z.device):
-                _lib.check(_lib.lib.dgll_hip_xent_reduce(_lib.raw_stream(z.device), row_loss.data_ptr(), target.data_ptr(), n, c, res.data_ptr()),
-                           "dgll_hip_xent_reduce")
+            _lib.launch("dgll_hip_xent_reduce", z.device, row_loss.data_ptr(), target.data_ptr(), n, c, res.data_ptr())
             ctx.reduction, ctx.soft = reduction, soft
             ctx.inv_count = res[3] if reduction == "mean" else None
             ctx.save_for_backward(z, target, None)

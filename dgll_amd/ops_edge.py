@@ -6,43 +6,28 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
 
 
 def _epv(dtype):
     return 8 if dtype == torch.bfloat16 else 4
 
 
-def _vec_ready(x):
-    """16-byte aligned rows: unit column stride, leading dimension a multiple of one vector."""
-    esz = x.element_size()
-    return (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= x.shape[1] and (x.stride(0) * esz) % 16 == 0
-            and x.data_ptr() % 16 == 0 and x.stride(0) >= -(-x.shape[1] // (16 // esz)) * (16 // esz))
-
-
-def _padded_copy(x, width=None):
-    """Copy of x whose leading dimension (and optionally logical width, zero filled) is vector aligned."""
-    epv = _epv(x.dtype)
-    width = x.shape[1] if width is None else width
-    ld = -(-width // epv) * epv
-    buf = torch.zeros((x.shape[0], ld), dtype=x.dtype, device=x.device)
-    buf[:, :x.shape[1]] = x
-    return buf[:, :width] if ld != width else buf
-
-
 def _ready(x):
-    return x if _vec_ready(x) else _padded_copy(x)
+    """x on 16-byte rows for kernels that load whole vectors and use the columns behind the last one: a copy has zeros there."""
+    return as_rows16(x, zero_pad=True)
 
 
 def _empty_padded(n, width, dtype, device):
-    epv = _epv(dtype)
-    ld = -(-width // epv) * epv
-    buf = torch.empty((n, ld), dtype=dtype, device=device)
-    return buf[:, :width] if ld != width else buf
+    return alloc_features(n, width, dtype, device, pad_to=_epv(dtype))
+
+
+def _ws(plan, heads, fo, dev, other_plan=None):
+    """(workspace or None, its size in bytes) of a GAT pass over `plan` (the larger of the two for a pass pair)."""
+    n = int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo))
+    if other_plan is not None:
+        n = max(n, int(_lib.lib.dgll_hip_gat_workspace_bytes(other_plan, heads, fo)))
+    return (torch.empty(n, dtype=torch.uint8, device=dev) if n else None), n
 
 
 # ------------------------------------------------------------------------------------------------ SDDMM
@@ -57,11 +42,8 @@ def sddmm_raw(graph, g, b):
     total = None
     for c0 in range(0, feat, tile):  # > 64 vectors per row: column blocks, summed
         gs, bs = _ready(g[:, c0:c0 + tile]), _ready(b[:, c0:c0 + tile])
-        with torch.cuda.device(g.device):
-            code = _lib.lib.dgll_hip_sddmm_csr(_stream(g.device), graph.rowptr.data_ptr(), graph.col.data_ptr(),
-                                               gs.data_ptr(), gs.stride(0), bs.data_ptr(), bs.stride(0), _dtype_code(gs),
-                                               out.data_ptr(), graph.n_rows, gs.shape[1])
-        _lib.check(code, "dgll_hip_sddmm_csr")
+        _lib.launch("dgll_hip_sddmm_csr", g.device, graph.rowptr.data_ptr(), graph.col.data_ptr(), gs.data_ptr(), gs.stride(0),
+                    bs.data_ptr(), bs.stride(0), _dtype_code(gs), out.data_ptr(), graph.n_rows, gs.shape[1])
         if feat > tile:
             total = out.clone() if total is None else total + out
     return out if total is None else total
@@ -78,11 +60,8 @@ class _SegmentMax(torch.autograd.Function):
         feat = x.shape[1]
         y = _empty_padded(graph.n_rows, feat, x.dtype, x.device)
         arg = torch.empty((graph.n_rows, y.stride(0)), dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            code = _lib.lib.dgll_hip_segment_max(_stream(x.device), graph.rowptr.data_ptr(), graph.col.data_ptr(),
-                                                 xs.data_ptr(), xs.stride(0), y.data_ptr(), arg.data_ptr(), y.stride(0),
-                                                 _dtype_code(xs), graph.n_rows, feat)
-        _lib.check(code, "dgll_hip_segment_max")
+        _lib.launch("dgll_hip_segment_max", x.device, graph.rowptr.data_ptr(), graph.col.data_ptr(), xs.data_ptr(), xs.stride(0),
+                    y.data_ptr(), arg.data_ptr(), y.stride(0), _dtype_code(xs), graph.n_rows, feat)
         ctx.save_for_backward(arg)
         ctx.n_src, ctx.graph, ctx.feat = x.shape[0], graph, feat
         return y
@@ -102,11 +81,8 @@ class _SegmentMax(torch.autograd.Function):
             t_rowptr, t_col = gt.rowptr, gt.col
         gs = _ready(g.to(arg.device))
         grad = _empty_padded(ctx.n_src, feat, g.dtype, g.device)
-        with torch.cuda.device(g.device):
-            code = _lib.lib.dgll_hip_segment_max_bwd(_stream(g.device), t_rowptr.data_ptr(), t_col.data_ptr(), gs.data_ptr(),
-                                                     gs.stride(0), arg.data_ptr(), arg.stride(0), grad.data_ptr(),
-                                                     grad.stride(0), _dtype_code(gs), ctx.n_src, feat)
-        _lib.check(code, "dgll_hip_segment_max_bwd")
+        _lib.launch("dgll_hip_segment_max_bwd", g.device, t_rowptr.data_ptr(), t_col.data_ptr(), gs.data_ptr(), gs.stride(0),
+                    arg.data_ptr(), arg.stride(0), grad.data_ptr(), grad.stride(0), _dtype_code(gs), ctx.n_src, feat)
         return grad, None
 
 
@@ -143,8 +119,7 @@ def _row_slot(x, byte_off, n_floats):
 
 def _empty_like_rows(n, like):
     """[n, like.shape[1]] with `like`'s row stride (the same padding behind every row)."""
-    buf = torch.empty((n, like.stride(0)), dtype=like.dtype, device=like.device)
-    return buf[:, :like.shape[1]] if like.stride(0) != like.shape[1] else buf
+    return alloc_features(n, like.shape[1], like.dtype, like.device, pad_to=like.stride(0))
 
 
 ROW_SCORES = os.environ.get("DGLL_GAT_ROW_SCORES", "1") != "0"     # 0: the forward always gathers T (A/B, tests)
@@ -180,10 +155,8 @@ def gat_dropout_mask(graph, heads, p, seed):
     out = torch.empty((graph.nnz, heads), dtype=torch.float32, device=dev)
     col = graph.col.contiguous()
     if dev.type == "cuda":
-        with torch.cuda.device(dev):
-            code = _lib.lib.dgll_hip_gat_dropout_mask(_stream(dev), graph.rowptr.data_ptr(), col.data_ptr(), graph.n_rows, heads,
-                                                      seed.data_ptr(), float(p), out.data_ptr())
-        _lib.check(code, "dgll_hip_gat_dropout_mask")
+        _lib.launch("dgll_hip_gat_dropout_mask", dev, graph.rowptr.data_ptr(), col.data_ptr(), graph.n_rows, heads, seed.data_ptr(),
+                    float(p), out.data_ptr())
     else:
         code = _lib.lib.dgll_host_gat_dropout_mask(graph.rowptr.data_ptr(), col.data_ptr(), graph.n_rows, heads, seed.data_ptr(), float(p),
                                                    out.data_ptr())
@@ -220,38 +193,24 @@ def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_score
     out = _empty_like_rows(graph.n_rows, h)
     rowsum = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
     plan = graph.plan()
-    ws_bytes = int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    timer = _launch_timer()
+    ws, ws_bytes = _ws(plan, heads, fo, dev)
     row_scores = attn2 is not None and not packed and ROW_SCORES and _rowscore_addressable(h)
     form = "packed" if packed else ("rowscore" if row_scores else "")
     if dropout is not None:
         form = (form + " dropout").strip()
-    end = timer.start(("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, form), dev) if timer else None
-    with torch.cuda.device(dev):
-        if dropout is not None:
-            a2 = attn2.detach().to(torch.float32).contiguous() if row_scores else None
-            code = _lib.lib.dgll_hip_gat_fwd_dropout(
-                _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                None if row_scores else t_gather.data_ptr(), 0 if row_scores else t_gather.stride(0),
-                a2.data_ptr() if row_scores else None, out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), graph.n_rows,
-                int(h.shape[0]), heads, fo, float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, ws_bytes,
-                dropout[0], dropout[1].data_ptr())
-        elif row_scores:
-            a2 = attn2.detach().to(torch.float32).contiguous()
-            code = _lib.lib.dgll_hip_gat_fwd_rowscore(
-                _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                a2.data_ptr(), out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), graph.n_rows, int(h.shape[0]), heads, fo,
-                float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, ws_bytes, 0, 0)
-        else:
-            code = _lib.lib.dgll_hip_gat_fwd_strided(
-                _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                t_gather.data_ptr(), t_gather.stride(0), out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(),
-                graph.n_rows, heads, fo, float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, ws_bytes)
-    if end is not None:
-        end.record(torch.cuda.current_stream(dev))
-    _lib.check(code, "dgll_hip_gat_fwd_dropout" if dropout is not None else
-               ("dgll_hip_gat_fwd_rowscore" if row_scores else "dgll_hip_gat_fwd_strided"))
+    a2 = attn2.detach().to(torch.float32).contiguous() if row_scores else None
+    # (entry, how the t_j reach the pass, the row count that bounds the gathered rows where the entry checks it, what follows ws)
+    if dropout is not None:
+        entry = "dgll_hip_gat_fwd_dropout"
+        scores = (None, 0, a2.data_ptr()) if row_scores else (t_gather.data_ptr(), t_gather.stride(0), None)
+        n_src, extra = (int(h.shape[0]),), (dropout[0], dropout[1].data_ptr())
+    elif row_scores:
+        entry, scores, n_src, extra = "dgll_hip_gat_fwd_rowscore", (a2.data_ptr(),), (int(h.shape[0]),), (0, 0)
+    else:
+        entry, scores, n_src, extra = "dgll_hip_gat_fwd_strided", (t_gather.data_ptr(), t_gather.stride(0)), (), ()
+    _lib.launch(entry, dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), *scores,
+                out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), graph.n_rows, *n_src, heads, fo, float(alpha),
+                int(apply_elu), _lib.ptr(ws), ws_bytes, *extra, tag=lambda: ("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, form))
     return h, s, t, out, rowsum, packed
 
 
@@ -274,12 +233,9 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
     grad_s = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
     grad_t = torch.empty((graph.n_cols, heads), dtype=torch.float32, device=dev)
     plan, t_plan = graph.plan(), gt.plan()
-    ws_bytes = max(int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo)),
-                   int(_lib.lib.dgll_hip_gat_workspace_bytes(t_plan, heads, fo)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    timer = _launch_timer()
-    tag = (heads, fo, str(h.dtype), graph.nnz, "packed" if packed else ("dropout" if dropout is not None else ""))
-    wsp = ws.data_ptr() if ws is not None else None
+    ws, ws_bytes = _ws(plan, heads, fo, dev, t_plan)
+    kind = (heads, fo, str(h.dtype), graph.nnz, "packed" if packed else ("dropout" if dropout is not None else ""))
+    wsp = _lib.ptr(ws)
     a1 = a2 = None
     gs_cols = grad_s
     if attn is not None:
@@ -290,46 +246,27 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
                 raise ValueError("the score-gradient epilogue needs a square adjacency (grad_S of the rows the transposed pass owns)")
             gs_cols = torch.zeros((graph.n_cols, heads), dtype=torch.float32, device=dev)
         a1, a2 = (v.detach().to(torch.float32).contiguous() for v in attn)
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and _rowscore_addressable(h)
-        end = timer.start(("gat", "bwd_rows") + (tag[:4] + (("rowscore " + tag[4]).strip(),) if rows_rowscore else tag), dev) if timer else None
-        if dropout is not None:
-            code = _lib.lib.dgll_hip_gat_bwd_rows_dropout(
-                st, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                None if rows_rowscore else t_gather.data_ptr(), 0 if rows_rowscore else t_gather.stride(0),
-                a2.data_ptr() if rows_rowscore else None, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h),
-                rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows,
-                int(h.shape[0]), heads, fo, alpha, apply_elu, wsp, ws_bytes, dropout[0], dropout[1].data_ptr())
-        elif rows_rowscore:      # t_j from the gathered rows, as in the forward
-            code = _lib.lib.dgll_hip_gat_bwd_rows_rowscore(
-                st, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), a2.data_ptr(),
+    rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and _rowscore_addressable(h)
+    # (entry, how the t_j reach the pass, the row count that bounds the gathered rows where the entry checks it, what follows ws)
+    if dropout is not None:
+        entry = "dgll_hip_gat_bwd_rows_dropout"
+        scores = (None, 0, a2.data_ptr()) if rows_rowscore else (t_gather.data_ptr(), t_gather.stride(0), None)
+        n_src, extra = (int(h.shape[0]),), (dropout[0], dropout[1].data_ptr())
+    elif rows_rowscore:      # t_j from the gathered rows, as in the forward
+        entry, scores, n_src, extra = "dgll_hip_gat_bwd_rows_rowscore", (a2.data_ptr(),), (int(h.shape[0]),), ()
+    else:
+        entry, scores, n_src, extra = "dgll_hip_gat_bwd_rows_strided", (t_gather.data_ptr(), t_gather.stride(0)), (), ()
+    _lib.launch(entry, dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), *scores,
                 out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h), rowsum.data_ptr(), dn.data_ptr(), dn.stride(0),
-                sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows, int(h.shape[0]), heads, fo, alpha, apply_elu, wsp, ws_bytes)
-        else:
-            code = _lib.lib.dgll_hip_gat_bwd_rows_strided(
-                st, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                t_gather.data_ptr(), t_gather.stride(0), out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h),
-                rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows,
-                heads, fo, alpha, apply_elu, wsp, ws_bytes)
-        if end is not None:
-            end.record(torch.cuda.current_stream(dev))
-        _lib.check(code, "dgll_hip_gat_bwd_rows_dropout" if dropout is not None else
-                   ("dgll_hip_gat_bwd_rows_rowscore" if rows_rowscore else "dgll_hip_gat_bwd_rows_strided"))
-        if gs_cols is not grad_s:
-            gs_cols[:graph.n_rows].copy_(grad_s)
-        end = timer.start(("gat", "bwd_cols") + tag, dev) if timer else None
-        cols_args = (st, t_plan, gt.rowptr.data_ptr(), gt.col.data_ptr(), dn.data_ptr(), dn.stride(0), h.data_ptr(), h.stride(0),
-                     t.data_ptr(), sd.data_ptr(), sd.stride(0), grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(h),
-                     graph.n_cols, heads, fo, alpha, wsp, ws_bytes, a1.data_ptr() if a1 is not None else None,
-                     a2.data_ptr() if a2 is not None else None, gs_cols.data_ptr() if a1 is not None else None)
-        if dropout is not None:
-            code = _lib.lib.dgll_hip_gat_bwd_cols_dropout(*cols_args, dropout[0], dropout[1].data_ptr())
-        else:
-            code = _lib.lib.dgll_hip_gat_bwd_cols_strided(*cols_args)
-        if end is not None:
-            end.record(torch.cuda.current_stream(dev))
-        _lib.check(code, "dgll_hip_gat_bwd_cols_dropout" if dropout is not None else "dgll_hip_gat_bwd_cols_strided")
+                sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows, *n_src, heads, fo, alpha, apply_elu, wsp, ws_bytes, *extra,
+                tag=lambda: ("gat", "bwd_rows") + (kind[:4] + (("rowscore " + kind[4]).strip(),) if rows_rowscore else kind))
+    if gs_cols is not grad_s:
+        gs_cols[:graph.n_rows].copy_(grad_s)
+    _lib.launch("dgll_hip_gat_bwd_cols_strided" if dropout is None else "dgll_hip_gat_bwd_cols_dropout", dev,
+                t_plan, gt.rowptr.data_ptr(), gt.col.data_ptr(), dn.data_ptr(), dn.stride(0), h.data_ptr(), h.stride(0),
+                t.data_ptr(), sd.data_ptr(), sd.stride(0), grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(h),
+                graph.n_cols, heads, fo, alpha, wsp, ws_bytes, _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(gs_cols if a1 is not None else None),
+                *(() if dropout is None else (dropout[0], dropout[1].data_ptr())), tag=lambda: ("gat", "bwd_cols") + kind)
     return grad_h, grad_s, grad_t
 
 
@@ -407,12 +344,6 @@ class _GatLayerStrided(torch.autograd.Function):
         return (grad_h if ctx.needs_input_grad[0] else None), grad_A, None, None, None, None, None, None, None, None
 
 
-def _launch_timer():
-    from .ops import LaunchTimer
-
-    return LaunchTimer.active
-
-
 class _GatAggregate(torch.autograd.Function):
     """out = act( sum_j w_ij scale_ij h_j / sum_j w_ij ) for all heads at once; see include/dgll_hip.h."""
 
@@ -429,15 +360,10 @@ class _GatAggregate(torch.autograd.Function):
         if edge_scale is not None:
             edge_scale = edge_scale.to(torch.float32).contiguous()
         plan = graph.plan()
-        ws_bytes = int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        with torch.cuda.device(dev):
-            code = _lib.lib.dgll_hip_gat_fwd(
-                _stream(dev), plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                t.data_ptr(), edge_scale.data_ptr() if edge_scale is not None else None, out.data_ptr(), out.stride(0),
-                _dtype_code(h), rowsum.data_ptr(), rowmax.data_ptr() if rowmax is not None else None, graph.n_rows, heads,
-                fo, float(alpha), int(apply_elu), int(mode), ws.data_ptr() if ws is not None else None, ws_bytes)
-        _lib.check(code, "dgll_hip_gat_fwd")
+        ws, ws_bytes = _ws(plan, heads, fo, dev)
+        _lib.launch("dgll_hip_gat_fwd", dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
+                    t.data_ptr(), _lib.ptr(edge_scale), out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), _lib.ptr(rowmax),
+                    graph.n_rows, heads, fo, float(alpha), int(apply_elu), int(mode), _lib.ptr(ws), ws_bytes)
         ctx.graph, ctx.cfg = graph, (heads, fo, float(alpha), int(apply_elu), int(mode))
         ctx.save_for_backward(h, s, t, edge_scale, out, rowsum, rowmax)
         return out
@@ -456,19 +382,12 @@ class _GatAggregate(torch.autograd.Function):
         grad_s = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
         grad_t = torch.empty((graph.n_cols, heads), dtype=torch.float32, device=dev)
         plan, t_plan = graph.plan(), gt.plan()
-        ws_bytes = max(int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo)),
-                       int(_lib.lib.dgll_hip_gat_workspace_bytes(t_plan, heads, fo)))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        with torch.cuda.device(dev):
-            code = _lib.lib.dgll_hip_gat_bwd(
-                _stream(dev), plan, t_plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), gt.rowptr.data_ptr(), gt.col.data_ptr(),
-                perm.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), t.data_ptr(),
-                edge_scale.data_ptr() if edge_scale is not None else None, out.data_ptr(), out.stride(0), g.data_ptr(),
-                g.stride(0), _dtype_code(h), rowsum.data_ptr(), rowmax.data_ptr() if rowmax is not None else None,
-                dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_h.data_ptr(), grad_h.stride(0), grad_s.data_ptr(),
-                grad_t.data_ptr(), graph.n_rows, graph.n_cols, heads, fo, alpha, apply_elu, mode,
-                ws.data_ptr() if ws is not None else None, ws_bytes)
-        _lib.check(code, "dgll_hip_gat_bwd")
+        ws, ws_bytes = _ws(plan, heads, fo, dev, t_plan)
+        _lib.launch("dgll_hip_gat_bwd", dev, plan, t_plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), gt.rowptr.data_ptr(),
+                    gt.col.data_ptr(), perm.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), t.data_ptr(), _lib.ptr(edge_scale),
+                    out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h), rowsum.data_ptr(), _lib.ptr(rowmax),
+                    dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_h.data_ptr(), grad_h.stride(0), grad_s.data_ptr(),
+                    grad_t.data_ptr(), graph.n_rows, graph.n_cols, heads, fo, alpha, apply_elu, mode, _lib.ptr(ws), ws_bytes)
         return grad_h, grad_s, grad_t, None, None, None, None, None, None, None
 
 
@@ -508,25 +427,14 @@ def gat_layer(graph, h, A, heads, alpha, apply_elu=True, pack_scores=False, drop
 
 # ------------------------------------------------------------------------------------------------ split launches
 # Building blocks of the partitioned GAT (dgll_amd/dist.py): the same kernels on the two column-halves of an adjacency.
-def _ws(plan, heads, fo, dev, other_plan=None):
-    n = int(_lib.lib.dgll_hip_gat_workspace_bytes(plan, heads, fo))
-    if other_plan is not None:
-        n = max(n, int(_lib.lib.dgll_hip_gat_workspace_bytes(other_plan, heads, fo)))
-    return (torch.empty(n, dtype=torch.uint8, device=dev) if n else None), n
-
-
 def gat_fwd_part(graph, h, s_rows, t_cols, out, rowsum, heads, fo, alpha, apply_elu, raw, accumulate):
     """One half of a split forward: rows of `graph` gather from `h` / `t_cols`; numerator into `out`, denominator into
     `rowsum` (raw), optionally on top of what a previous launch left there (accumulate)."""
     dev = h.device
     ws, nbytes = _ws(graph.plan(), heads, fo, dev)
-    with torch.cuda.device(dev):
-        code = _lib.lib.dgll_hip_gat_fwd_ex(
-            _stream(dev), graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0),
-            s_rows.data_ptr(), t_cols.data_ptr(), None, out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(),
-            graph.n_rows, heads, fo, float(alpha), int(apply_elu), ws.data_ptr() if ws is not None else None, nbytes,
-            int(raw), int(accumulate))
-    _lib.check(code, "dgll_hip_gat_fwd_ex")
+    _lib.launch("dgll_hip_gat_fwd_ex", dev, graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0),
+                s_rows.data_ptr(), t_cols.data_ptr(), None, out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(),
+                graph.n_rows, heads, fo, float(alpha), int(apply_elu), _lib.ptr(ws), nbytes, int(raw), int(accumulate))
 
 
 def gat_bwd_rows_part(graph, h_cols, s_rows, t_cols, out, g, rowsum, dn, dd, grad_s, heads, fo, alpha, apply_elu, accumulate,
@@ -537,24 +445,18 @@ def gat_bwd_rows_part(graph, h_cols, s_rows, t_cols, out, g, rowsum, dn, dd, gra
     exact pass (dgll_hip_gat_bwd_rows_split)."""
     dev = out.device
     ws, nbytes = _ws(graph.plan(), heads, fo, dev)
-    with torch.cuda.device(dev):
-        if int(accumulate) >= 4:
-            if partial is None or partial.dtype != torch.float32 or partial.numel() < graph.n_rows * 3 * heads or not partial.is_contiguous():
-                raise ValueError("a split exact rows pass needs a contiguous fp32 [n_rows, 3 * heads] `partial` buffer")
-            code = _lib.lib.dgll_hip_gat_bwd_rows_split(
-                _stream(dev), graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h_cols.data_ptr(), h_cols.stride(0),
-                s_rows.data_ptr(), t_cols.data_ptr(), out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(out),
-                rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(), graph.n_rows, heads, fo,
-                float(alpha), int(apply_elu), int(accumulate), partial.data_ptr(), ws.data_ptr() if ws is not None else None, nbytes)
-            _lib.check(code, "dgll_hip_gat_bwd_rows_split")
-            return
-        code = _lib.lib.dgll_hip_gat_bwd_rows(
-            _stream(dev), graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h_cols.data_ptr(), h_cols.stride(0),
-            s_rows.data_ptr(), t_cols.data_ptr(), None, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0),
-            _dtype_code(out), rowsum.data_ptr(), None, dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(),
-            graph.n_rows, heads, fo, float(alpha), int(apply_elu), 0, int(accumulate), ws.data_ptr() if ws is not None else None,
-            nbytes)
-    _lib.check(code, "dgll_hip_gat_bwd_rows")
+    head = (graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h_cols.data_ptr(), h_cols.stride(0), s_rows.data_ptr(),
+            t_cols.data_ptr())
+    if int(accumulate) >= 4:
+        if partial is None or partial.dtype != torch.float32 or partial.numel() < graph.n_rows * 3 * heads or not partial.is_contiguous():
+            raise ValueError("a split exact rows pass needs a contiguous fp32 [n_rows, 3 * heads] `partial` buffer")
+        _lib.launch("dgll_hip_gat_bwd_rows_split", dev, *head, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(out),
+                    rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(), graph.n_rows, heads, fo,
+                    float(alpha), int(apply_elu), int(accumulate), partial.data_ptr(), _lib.ptr(ws), nbytes)
+        return
+    _lib.launch("dgll_hip_gat_bwd_rows", dev, *head, None, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(out),
+                rowsum.data_ptr(), None, dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(), graph.n_rows, heads, fo,
+                float(alpha), int(apply_elu), 0, int(accumulate), _lib.ptr(ws), nbytes)
 
 
 def gat_bwd_cols_part(graph_t, dn, h_rows, t_rows, s_cols, dd_cols, grad_h, grad_t, heads, fo, alpha):
@@ -562,10 +464,7 @@ def gat_bwd_cols_part(graph_t, dn, h_rows, t_rows, s_cols, dd_cols, grad_h, grad
     destination rows with dn / s_cols / dd_cols)."""
     dev = dn.device
     ws, nbytes = _ws(graph_t.plan(), heads, fo, dev)
-    with torch.cuda.device(dev):
-        code = _lib.lib.dgll_hip_gat_bwd_cols(
-            _stream(dev), graph_t.plan(), graph_t.rowptr.data_ptr(), graph_t.col.data_ptr(), None, dn.data_ptr(), dn.stride(0),
-            h_rows.data_ptr(), h_rows.stride(0), t_rows.data_ptr(), s_cols.data_ptr(), dd_cols.data_ptr(), None, None,
-            grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(dn), graph_t.n_rows, heads, fo, float(alpha), 0,
-            ws.data_ptr() if ws is not None else None, nbytes)
-    _lib.check(code, "dgll_hip_gat_bwd_cols")
+    _lib.launch("dgll_hip_gat_bwd_cols", dev, graph_t.plan(), graph_t.rowptr.data_ptr(), graph_t.col.data_ptr(), None, dn.data_ptr(),
+                dn.stride(0), h_rows.data_ptr(), h_rows.stride(0), t_rows.data_ptr(), s_cols.data_ptr(), dd_cols.data_ptr(), None, None,
+                grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(dn), graph_t.n_rows, heads, fo, float(alpha), 0,
+                _lib.ptr(ws), nbytes)

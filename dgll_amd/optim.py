@@ -206,8 +206,8 @@ class FlatAdam(torch.optim.Optimizer):
             begin = i64(*[self.offsets[i] for i in idx])
             end = i64(*[self.offsets[i] + self.params[i].numel() for i in idx])
             cols = (C.c_int * max(n, 1))(*[self.params[i].shape[1] for i in idx])
-            pk = vp(*[self._packed[i][0].data_ptr() if self._packed[i][0] is not None else None for i in idx])
-            ld = i64(*[self._packed[i][0].stride(0) if self._packed[i][0] is not None else 0 for i in idx])
+            pk = vp(*[_lib.ptr(self._packed[i][0]) for i in idx])
+            ld = i64(*[_lib.pitch(self._packed[i][0]) for i in idx])
             pkt = vp(*[self._packed[i][1].data_ptr() for i in idx])
             ldt = i64(*[self._packed[i][1].stride(0) for i in idx])
             self._table = (n, begin, end, cols, pk, ld, pkt, ldt)
@@ -256,12 +256,9 @@ class FlatAdam(torch.optim.Optimizer):
             n, sb, se, cols, pk, ld, pkt, ldt = self._segments() if whole else self._segments_in(begin, end)
         else:
             n, sb, se, cols, pk, ld, pkt, ldt = (0, None, None, None, None, None, None, None)
-        with _lib.on_device(self.device):
-            code = _lib.lib.dgll_hip_adam_flat(
-                _lib.raw_stream(self.device), self.flat.data_ptr() + 4 * begin, self.grad.data_ptr() + 4 * begin,
-                self.exp_avg.data_ptr() + 4 * begin, self.exp_avg_sq.data_ptr() + 4 * begin, end - begin, lr, betas[0], betas[1], eps,
-                weight_decay, step_no, scale, n, sb, se, cols, pk, ld, pkt, ldt)
-        _lib.check(code, "dgll_hip_adam_flat")
+        _lib.launch("dgll_hip_adam_flat", self.device, self.flat.data_ptr() + 4 * begin, self.grad.data_ptr() + 4 * begin,
+                    self.exp_avg.data_ptr() + 4 * begin, self.exp_avg_sq.data_ptr() + 4 * begin, end - begin, lr, betas[0], betas[1], eps,
+                    weight_decay, step_no, scale, n, sb, se, cols, pk, ld, pkt, ldt)
 
     def _segments_in(self, begin, end):
         """The packed-weight table of the parameters inside [begin, end), offsets relative to `begin` (a partial update)."""
@@ -270,8 +267,8 @@ class FlatAdam(torch.optim.Optimizer):
         i64, vp = C.c_int64 * max(n, 1), C.c_void_p * max(n, 1)
         return (n, i64(*[self.offsets[i] - begin for i in idx]), i64(*[self.offsets[i] + self.params[i].numel() - begin for i in idx]),
                 (C.c_int * max(n, 1))(*[self.params[i].shape[1] for i in idx]),
-                vp(*[self._packed[i][0].data_ptr() if self._packed[i][0] is not None else None for i in idx]),
-                i64(*[self._packed[i][0].stride(0) if self._packed[i][0] is not None else 0 for i in idx]),
+                vp(*[_lib.ptr(self._packed[i][0]) for i in idx]),
+                i64(*[_lib.pitch(self._packed[i][0]) for i in idx]),
                 vp(*[self._packed[i][1].data_ptr() for i in idx]), i64(*[self._packed[i][1].stride(0) for i in idx]))
 
     def _update_host(self, begin, end, lr, betas, eps, weight_decay, step_no, scale):

@@ -569,10 +569,8 @@ class MiniBatchPipeline:
                 ids = torch.empty(int(pos.numel()), dtype=torch.int64, device=self.device)
                 from . import _lib
 
-                with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib.dgll_hip_translate_positions(self.load_stream.cuda_stream, indptr.data_ptr(), indices.data_ptr(),
-                                                                     seeds_d.data_ptr(), ptr_d.data_ptr(), int(n_rows), pos_d.data_ptr(),
-                                                                     pos_d.element_size(), ids.data_ptr()), "dgll_hip_translate_positions")
+                _lib.launch("dgll_hip_translate_positions", self.device, indptr.data_ptr(), indices.data_ptr(), seeds_d.data_ptr(),
+                            ptr_d.data_ptr(), int(n_rows), pos_d.data_ptr(), pos_d.element_size(), ids.data_ptr(), stream=self.load_stream)
             else:
                 hop_seeds, counts = sg.pending_positions if device_inputs is None else device_inputs
                 seeds_d = hop_seeds.to(self.device, non_blocking=True)
@@ -894,15 +892,14 @@ class MiniBatchPipeline:
                 d.rowptr_cap[h] = step.rows[h]
         d.cache, d.ldc, d.host, d.ldh, d.slot, d.host_map = cptr, ldc, hptr, ldh, sptr, mptr
         d.feat, d.dtype = self.cache.total_dim, _dtype_code(st.feat_all)
-        d.miss_count = counter.data_ptr() if counter is not None else None
+        d.miss_count = _lib.ptr(counter)
         d.ld_feat = st.feat_all.stride(0)
         d.reduced_out, d.ld_reduced = st.reduced.data_ptr(), st.reduced.stride(0)
         d.reduce = _lib.REDUCE_MEAN if self.reduce_last_hop == "mean" else _lib.REDUCE_SUM
         d.ids_out = ids_dev.data_ptr()
         self._bind_miss_stage(d, stream, which, sptr is not None, n_outer)
         d.labels, d.labels_out, d.labels_cap, d.label_fill = self._labels_dev.data_ptr(), st.labels.data_ptr(), step.rows[0], -100
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.dgll_hip_load_sampled_batch(stream.cuda_stream, C.byref(d)), "dgll_hip_load_sampled_batch")
+        _lib.launch("dgll_hip_load_sampled_batch", self.device, C.byref(d), stream=stream)
         done = torch.cuda.Event()
         done.record(stream)
         self.cache.native_load_end(stream, counter, keep, sum(n[:L]) + n_outer, done)

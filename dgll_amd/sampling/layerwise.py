@@ -50,14 +50,6 @@ _ERRORS = {1: "a row id outside [0, N)", 2: "a column id outside [0, N)", 4: "mo
            8: "a local column id >= 4096"}
 
 
-def _vp(t):
-    return None if t is None else t.data_ptr()
-
-
-def _raw(stream):
-    return stream.cuda_stream
-
-
 def _shift_for(bound):
     """Fixed-point exponent for column masses that can reach `bound`: every mass (and its 64-bit sum) stays below 2^61."""
     bound = float(bound)
@@ -109,9 +101,8 @@ class ColumnMass:
     def p_of(self, ids, count=None, stream=None):
         """fp64 p of int64 device ids (the first *count of them when count is a device scalar)."""
         out = torch.empty(ids.numel(), dtype=torch.float64, device=ids.device)
-        st = torch.cuda.current_stream(ids.device) if stream is None else stream
-        _lib.check(_lib.lib.dgll_hip_lw_column_p(_raw(st), ids.data_ptr(), _vp(count), ids.numel(), self.ws.mass.data_ptr(), self.shift,
-                                                 int(self.flat), self.totals.data_ptr(), out.data_ptr()), "dgll_hip_lw_column_p")
+        _lib.launch("dgll_hip_lw_column_p", ids.device, ids.data_ptr(), _lib.ptr(count), ids.numel(), self.ws.mass.data_ptr(), self.shift,
+                    int(self.flat), self.totals.data_ptr(), out.data_ptr(), stream=stream)
         return out
 
     def candidates(self):
@@ -132,7 +123,6 @@ def column_mass(L, rows=None, flat=False, ws=None, info=None, shift=None, stream
     columns.  No host synchronisation."""
     if ws is None:
         ws = Workspace(L.n_cols, L.device)
-    st = torch.cuda.current_stream(L.device) if stream is None else stream
     if info is None:
         info = torch.zeros(_INFO_WORDS, dtype=torch.int64, device=L.device)
     n_rows = L.n_rows if rows is None else int(rows.numel())
@@ -141,9 +131,9 @@ def column_mass(L, rows=None, flat=False, ws=None, info=None, shift=None, stream
         shift = _shift_for(n_rows * vmax)
     totals = torch.empty(2, dtype=torch.int64, device=L.device)
     seg = None if rows is None else torch.empty(n_rows + 1, dtype=torch.int64, device=L.device)
-    _lib.check(_lib.lib.dgll_hip_lw_column_mass(_raw(st), L.rowptr.data_ptr(), L.col.data_ptr(), _vp(L.val), _vp(rows), n_rows, ws.n,
-                                                ws.marker.data_ptr(), ws.next_epoch(), ws.mass.data_ptr(), shift, int(flat),
-                                                ws.cand.data_ptr(), info.data_ptr(), totals.data_ptr(), _vp(seg)), "dgll_hip_lw_column_mass")
+    _lib.launch("dgll_hip_lw_column_mass", L.device, L.rowptr.data_ptr(), L.col.data_ptr(), _lib.ptr(L.val), _lib.ptr(rows), n_rows, ws.n,
+                ws.marker.data_ptr(), ws.next_epoch(), ws.mass.data_ptr(), shift, int(flat), ws.cand.data_ptr(), info.data_ptr(),
+                totals.data_ptr(), _lib.ptr(seg), stream=stream)
     return ColumnMass(ws, info[0:1], shift, flat, totals)
 
 
@@ -167,26 +157,23 @@ def select(mass, fanout, seed, layer=0, info=None, stream=None):
     fanout = int(fanout)
     if not 1 <= fanout <= ws.win_cap - 1024:
         raise ValueError("fanout must be in [1, %d]" % (ws.win_cap - 1024))
-    st = torch.cuda.current_stream(ws.device) if stream is None else stream
     if info is None:
         info = torch.zeros(_INFO_WORDS, dtype=torch.int64, device=ws.device)
     out = torch.empty(fanout, dtype=torch.int64, device=ws.device)
-    _lib.check(_lib.lib.dgll_hip_lw_select(_raw(st), ws.cand.data_ptr(), mass.count.data_ptr(), ws.n, ws.mass.data_ptr(), mass.shift,
-                                           int(mass.flat), int(seed) & 0xFFFFFFFFFFFFFFFF, int(layer), fanout, ws.keys.data_ptr(),
-                                           ws.ctrl.data_ptr(), ws.win_key.data_ptr(), ws.win_id.data_ptr(), ws.win_cap, out.data_ptr(),
-                                           info.data_ptr()), "dgll_hip_lw_select")
+    _lib.launch("dgll_hip_lw_select", ws.device, ws.cand.data_ptr(), mass.count.data_ptr(), ws.n, ws.mass.data_ptr(), mass.shift,
+                int(mass.flat), int(seed) & 0xFFFFFFFFFFFFFFFF, int(layer), fanout, ws.keys.data_ptr(), ws.ctrl.data_ptr(),
+                ws.win_key.data_ptr(), ws.win_id.data_ptr(), ws.win_cap, out.data_ptr(), info.data_ptr(), stream=stream)
     return out, info
 
 
 def union_sorted(ws, a, a_count, b, info, stream=None):
     """sorted unique(a[:*a_count] u b) on the device (FastGCN's np.unique(concatenate(S, batch))); length into info[2]."""
-    st = torch.cuda.current_stream(ws.device) if stream is None else stream
     cap = a.numel() + b.numel()
     reps = torch.empty(cap, dtype=torch.int64, device=ws.device)
     out = torch.empty(cap, dtype=torch.int64, device=ws.device)
-    _lib.check(_lib.lib.dgll_hip_lw_union_sorted(_raw(st), a.data_ptr(), a_count.data_ptr(), a.numel(), b.data_ptr(), b.numel(), ws.n,
-                                                 ws.marker.data_ptr(), ws.next_epoch(), reps.data_ptr(), ws.n_reps.data_ptr(),
-                                                 out.data_ptr(), info.data_ptr()), "dgll_hip_lw_union_sorted")
+    _lib.launch("dgll_hip_lw_union_sorted", ws.device, a.data_ptr(), a_count.data_ptr(), a.numel(), b.data_ptr(), b.numel(), ws.n,
+                ws.marker.data_ptr(), ws.next_epoch(), reps.data_ptr(), ws.n_reps.data_ptr(), out.data_ptr(), info.data_ptr(),
+                stream=stream)
     return out
 
 
@@ -203,11 +190,10 @@ def inverse_weights(p, s, count=None, stream=None):
 
 
 def _weights(p, count, snum_dev, snum, n_total, mode, stream):
-    st = torch.cuda.current_stream(p.device) if stream is None else stream
     p = p.to(torch.float64).contiguous()
     w = torch.empty_like(p)
-    _lib.check(_lib.lib.dgll_hip_lw_weights(_raw(st), p.data_ptr(), _vp(count), p.numel(), _vp(snum_dev), snum, int(n_total), mode,
-                                            w.data_ptr()), "dgll_hip_lw_weights")
+    _lib.launch("dgll_hip_lw_weights", p.device, p.data_ptr(), _lib.ptr(count), p.numel(), _lib.ptr(snum_dev), snum, int(n_total), mode, w.data_ptr(),
+                stream=stream)
     return w
 
 
@@ -217,7 +203,6 @@ def extract_block(L, rows, cols, weights, ws=None, info=None, count=None, sorted
     at most 4096).  One blocking read (the column count and the nnz)."""
     if ws is None:
         ws = Workspace(L.n_cols, L.device)
-    st = torch.cuda.current_stream(L.device) if stream is None else stream
     if info is None:
         info = torch.zeros(_INFO_WORDS, dtype=torch.int64, device=L.device)
     if count is None:
@@ -233,10 +218,9 @@ def extract_block(L, rows, cols, weights, ws=None, info=None, count=None, sorted
         bitmap = torch.empty(n_rows * (MAX_FANOUT // 32), dtype=torch.int32, device=L.device)
         below = torch.empty(n_rows * (MAX_FANOUT // 32), dtype=torch.int32, device=L.device)
     epoch = ws.next_epoch()
-    _lib.check(_lib.lib.dgll_hip_lw_block_count(_raw(st), L.rowptr.data_ptr(), L.col.data_ptr(), rows.data_ptr(), n_rows, ws.n,
-                                                cols.data_ptr(), count.data_ptr(), cols.numel(), ws.mark.data_ptr(), ws.local.data_ptr(),
-                                                epoch, int(sorted_cols), _vp(seg), _vp(bitmap), _vp(below), rowptr.data_ptr(),
-                                                info.data_ptr()), "dgll_hip_lw_block_count")
+    _lib.launch("dgll_hip_lw_block_count", L.device, L.rowptr.data_ptr(), L.col.data_ptr(), rows.data_ptr(), n_rows, ws.n, cols.data_ptr(),
+                count.data_ptr(), cols.numel(), ws.mark.data_ptr(), ws.local.data_ptr(), epoch, int(sorted_cols), _lib.ptr(seg), _lib.ptr(bitmap),
+                _lib.ptr(below), rowptr.data_ptr(), info.data_ptr(), stream=stream)
     h = info.cpu().tolist()           # the one blocking read of the layer
     if h[4]:
         raise RuntimeError("layer-wise sampler: " + ", ".join(m for bit, m in _ERRORS.items() if h[4] & bit))
@@ -245,10 +229,9 @@ def extract_block(L, rows, cols, weights, ws=None, info=None, count=None, sorted
     col = torch.empty(nnz, dtype=torch.int32, device=L.device)
     val = torch.empty(nnz, dtype=torch.float32, device=L.device)
     w = weights.to(torch.float64).contiguous()
-    _lib.check(_lib.lib.dgll_hip_lw_block_fill(_raw(st), L.rowptr.data_ptr(), L.col.data_ptr(), _vp(L.val), rows.data_ptr(), n_rows, ws.n,
-                                               ws.mark.data_ptr(), ws.local.data_ptr(), epoch, w.data_ptr(), int(sorted_cols), m,
-                                               _vp(seg), _vp(bitmap), _vp(below), rowptr.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                               info.data_ptr()), "dgll_hip_lw_block_fill")
+    _lib.launch("dgll_hip_lw_block_fill", L.device, L.rowptr.data_ptr(), L.col.data_ptr(), _lib.ptr(L.val), rows.data_ptr(), n_rows, ws.n,
+                ws.mark.data_ptr(), ws.local.data_ptr(), epoch, w.data_ptr(), int(sorted_cols), m, _lib.ptr(seg), _lib.ptr(bitmap), _lib.ptr(below),
+                rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), info.data_ptr(), stream=stream)
     return CSRGraph(rowptr, col, val, n_rows, m, check=False), m, h
 
 
