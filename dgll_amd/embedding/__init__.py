@@ -8,11 +8,13 @@ launch (a lane per walk, Philox4x32-10 keyed by the seed, counter = (walk index,
 batch is three launches (scores, W_out update, W_in update).
 
 Functions:
-    random_walks(g, starts, length, p=1.0, q=1.0, seed=0, first_walk_index=0, stream=None) -> int32 [n, length], -1 after a dead end
+    random_walks(g, starts, length, p=1.0, q=1.0, seed=0, first_walk_index=0, stream=None, info=None, weighted=False, alias=None)
+                                                         -> int32 [n, length], -1 after a dead end
+    AliasTable.from_graph(g)                             per-row alias tables of the edge values, 8 bytes per edge, cached on g
     NoiseTable(weights) / NoiseTable.from_graph(g)       fixed-point cumulative noise distribution (in-degree^0.75 by default)
     sgns_negatives(walks, window, negatives, noise, seed, first_walk_index=0) -> int32 [n, L, 2W, K], -1 where there is no pair
     sgns_step(W_in, W_out, walks, window, negatives, noise, lr, seed, first_walk_index=0) -> loss sum (fp64 device scalar)
-Classes (constructor arguments as in the reference, plus keyword-only extras):
+Classes (constructor arguments as in the reference, plus keyword-only extras, `weighted=False` among them):
     SkipGramModel(totalNodes, embedDim)                                                      skipgram.py:3-26
     DeepWalk(graph, walkLength, embedDim, numbOfWalksPerVertex, windowSize, lr)             deepWalk.py:13-85
     Node2vec(graph, walkLength, embedDim, numbOfWalksPerVertex, windowSize, lr, p, q)       node2vec.py:13-118
@@ -29,10 +31,16 @@ Documented differences (the reference's behaviour is not reproduced here):
   (d) `numbOfWalksPerVertex == 0` selects the default (3).  The reference tests `== 3` (randomWalkEmbedding.py:25).
   (e) The draws are not bit-equal to Python's `random` or `np.random.choice` (a different generator); the node2vec transition
       probabilities are the reference's (tests/golden/node2vec_probs.npz).
-  (f) Edge weights are ignored: walks are unweighted.
+  (f) Edge weights are ignored unless `weighted=True` is given (the default may change later).  With it every transition is
+      multiplied by the edge's weight -- P(x | t, v) proportional to w_vx * bias(t, x), the reference's computeProbabilities
+      (tests/golden/node2vec_probs_weighted.npz) -- drawn from a per-row alias table with the p/q rejection step on top.  An edge
+      of weight 0 is never walked; a node whose out-weights sum to 0 ends the walk (the reference divides by 0 there).
+      `DeepWalk(..., weighted=True)` is a weighted first-order walk, which the reference's DeepWalk does not have.
+  (g) With `weighted=True` the first step is weighted too, as in standard node2vec; the reference's first step is uniform
+      (node2vec.py:59).
 DeepWalk on a node without out-edges ends the walk (the reference raises); node2vec stops there in both.
 struc2vec, the classifiers and the plotting helpers are not provided.
 """
-from .walks import random_walks, walk_info, MAX_ATTEMPTS  # noqa: F401
+from .walks import AliasTable, random_walks, walk_info, MAX_ATTEMPTS  # noqa: F401
 from .sgns import NoiseTable, sgns_negatives, sgns_step  # noqa: F401
 from .models import SkipGramModel, RandomWalkEmbedding, DeepWalk, Node2vec  # noqa: F401

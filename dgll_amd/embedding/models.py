@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from ..graph import CSRGraph
 from .sgns import NoiseTable, sgns_step
-from .walks import as_walk_graph, random_walks, walk_info
+from .walks import AliasTable, as_walk_graph, random_walks, walk_info
 
 
 class SkipGramModel(nn.Module):
@@ -31,8 +31,9 @@ class SkipGramModel(nn.Module):
         return torch.matmul(torch.matmul(features.to(self.W1.device), self.W1), self.W2)
 
 
-def _encode_graph(graph, device):
-    """(CSRGraph on the device, sorted node labels or None).  networkx graphs: labels are encoded by their sorted order."""
+def _encode_graph(graph, device, weighted=False):
+    """(CSRGraph on the device, sorted node labels or None).  networkx graphs: labels are encoded by their sorted order; with
+    `weighted` the edges carry their `weight` attribute, 1 where it is missing (node2vec.py:43-47)."""
     from ..data.dgraph import DGraph
 
     if isinstance(graph, (CSRGraph, DGraph)):
@@ -41,25 +42,29 @@ def _encode_graph(graph, device):
         raise TypeError("graph must be a networkx graph, a CSRGraph or a DGraph, got %r" % type(graph))
     labels = sorted(graph.nodes())
     code = {v: i for i, v in enumerate(labels)}
-    src, dst = [], []
+    src, dst, val = [], [], []
     for v, nbrs in graph.adjacency():
         cv = code[v]
-        for u in nbrs:
+        for u, attr in nbrs.items():
             src.append(cv)
             dst.append(code[u])
+            if weighted:
+                val.append(attr.get("weight", 1))
     n = len(labels)
-    g = CSRGraph.from_coo(torch.tensor(src, dtype=torch.int64), torch.tensor(dst, dtype=torch.int64), None, (n, n))
+    g = CSRGraph.from_coo(torch.tensor(src, dtype=torch.int64), torch.tensor(dst, dtype=torch.int64),
+                          torch.tensor(val, dtype=torch.float32) if weighted else None, (n, n))
     return g.to(device), labels
 
 
 class RandomWalkEmbedding:
     """randomWalkEmbedding.py:9-66 with the training loop both subclasses share.
     Keyword-only extras: negatives (K per pair), batch_walks (walks per launch and per synchronous step), seed (None: drawn from
-    numpy's global generator), device."""
+    numpy's global generator), device, weighted (walk in proportion to the edge weights: networkx's `weight` attribute or the
+    CSR's values; the table is built here, once)."""
     p = q = 1.0
 
     def __init__(self, graph, walkLength, embedDim, numbOfWalksPerVertex, windowSize, lr, negatives=5, batch_walks=1024, seed=None,
-                 device=None):
+                 device=None, weighted=False):
         self.graph = graph
         if walkLength == 0:
             self.walkLength = 3
@@ -89,7 +94,8 @@ class RandomWalkEmbedding:
         if device is None:
             device = graph.device if isinstance(graph, CSRGraph) and graph.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
-        self.csr, self.labels = _encode_graph(graph, self.device)
+        self.csr, self.labels = _encode_graph(graph, self.device, bool(weighted))
+        self.alias = AliasTable.from_graph(self.csr) if weighted else None
         self._code = None if self.labels is None else {v: i for i, v in enumerate(self.labels)}
         self.totalNodes = self.csr.n_rows
         self.negatives, self.batch_walks = int(negatives), int(batch_walks)
@@ -120,7 +126,8 @@ class RandomWalkEmbedding:
 
     # ---- walks -------------------------------------------------------------------------------------------------------------
     def _walk_batch(self, starts, length, info=None):
-        walks = random_walks(self.csr, starts, length, p=self.p, q=self.q, seed=self.seed, first_walk_index=self._walks_drawn, info=info)
+        walks = random_walks(self.csr, starts, length, p=self.p, q=self.q, seed=self.seed, first_walk_index=self._walks_drawn, info=info,
+                             alias=self.alias)
         first = self._walks_drawn
         self._walks_drawn += int(starts.numel())
         return walks, first
@@ -168,7 +175,7 @@ class RandomWalkEmbedding:
 
 
 class DeepWalk(RandomWalkEmbedding):
-    """deepWalk.py:13-85: uniform walks."""
+    """deepWalk.py:13-85: uniform walks; weighted=True: first-order walks in proportion to the edge weights."""
 
     def __init__(self, graph=None, walkLength=0, embedDim=0, numbOfWalksPerVertex=0, windowSize=0, lr=0, **kw):
         if graph is None:
@@ -178,7 +185,8 @@ class DeepWalk(RandomWalkEmbedding):
 
 
 class Node2vec(RandomWalkEmbedding):
-    """node2vec.py:13-118: second-order walks with return parameter p and in-out parameter q (0 selects 0.5 and 0.8)."""
+    """node2vec.py:13-118: second-order walks with return parameter p and in-out parameter q (0 selects 0.5 and 0.8); weighted=True
+    multiplies every transition by the edge's weight, as the reference's computeProbabilities does."""
 
     def __init__(self, graph=None, walkLength=0, embedDim=0, numbOfWalksPerVertex=0, windowSize=0, lr=0, p=0, q=0, **kw):
         if graph is None:

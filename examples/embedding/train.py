@@ -4,6 +4,7 @@ device (dgll_amd.embedding).  Prints the loss of every epoch and the mean cosine
 
     python examples/embedding/train.py --method deepwalk
     python examples/embedding/train.py --method node2vec --p 0.5 --q 2 --communities 8 --nodes 4000 --dim 64
+    python examples/embedding/train.py --method node2vec --weighted      # edges inside a community weigh 4, the others 1
 """
 import argparse
 import os
@@ -58,12 +59,16 @@ def main():
     ap.add_argument("--q", type=float, default=2.0)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--weighted", action="store_true", help="walk in proportion to edge weights (4 inside a community, 1 across)")
     args = ap.parse_args()
 
     dev = torch.device("cuda:0")
     g, comm = planted_partition(args.nodes, args.communities, 12, 1, args.seed)
     g = g.to(dev)
-    kw = dict(negatives=args.negatives, batch_walks=args.batch_walks, seed=args.seed)
+    if args.weighted:
+        same = torch.from_numpy(comm)[g.row_index().cpu()] == torch.from_numpy(comm)[g.col.cpu().long()]
+        g = g.with_values(torch.where(same, 4.0, 1.0).to(dev))
+    kw = dict(negatives=args.negatives, batch_walks=args.batch_walks, seed=args.seed, weighted=args.weighted)
     if args.method == "deepwalk":
         emb = embedding.DeepWalk(g, args.walk_length, args.dim, args.walks_per_vertex, args.window, args.lr, **kw)
     else:

@@ -683,7 +683,7 @@ int dgll_host_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint
 
 /* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
  * Every random word is Philox4x32-10 with key = {seed lo, seed hi}.
- * Walks: CSR (int64 rowptr, int32 col, rows ascending when p or q != 1; edge values do not exist here: walks are unweighted)
+ * Walks: CSR (int64 rowptr, int32 col, rows ascending when p or q != 1; dgll_hip_random_walk ignores edge values)
  * over n_nodes nodes, every row shorter than 2^32; starts int64[n]; walks int32[n, length] row-major, walks[i, 0] = starts[i].
  * A node without out-edges ends the walk: every later entry is -1.  Walk i has the global index g = first_walk_index + i and step
  * s >= 1, attempt a >= 0 use the counter {g lo, g hi, s, a}: word 0 picks the candidate col[rowptr[v] + mulhi32(x0, deg)], word 1
@@ -697,6 +697,22 @@ int dgll_hip_random_walk(void* stream, const int64_t* rowptr, const int32_t* col
                          int64_t* info);
 /* The three thresholds of dgll_hip_random_walk, {return, common neighbour, far} (host; for tests and restatements).            */
 int dgll_host_node2vec_thresholds(double p, double q, uint64_t* out3);
+/* Per-row alias tables for edge-weighted walks: table uint32[nnz, 2] (8-byte aligned), entry e of a row that starts at b and has
+ * deg entries = {T, alias}: a draw is slot = mulhi32(x0, deg), edge = b + (x1 < T[b + slot] ? slot : alias[b + slot]), alias local
+ * to the row (< deg).  Vose's construction, one lane per row, in float64 (q = val deg / sum(val), T = round(2^32 q) clamped to
+ * 2^32 - 1) and in a fixed order: two builds give the same bits.  A slot that always keeps itself is {2^32 - 1, slot}.  val: fp32
+ * [nnz], finite and >= 0; an edge of weight 0 is never drawn.  A row whose weights sum to 0 holds {0, slot} in every slot (no other
+ * row holds such an entry) and is a dead end for the walks.  A negative, NaN or infinite weight sets bit 4 of info[1] (int64[2],
+ * zeroed by the caller; info[0] is not written) and leaves its row a dead end.  scratch: 12 bytes per edge, 8-byte aligned.    */
+int dgll_hip_alias_build(void* stream, const int64_t* rowptr, const float* val, int64_t n_rows, int64_t nnz, void* scratch,
+                         size_t scratch_bytes, uint32_t* table, int64_t* info);
+/* dgll_hip_random_walk with the candidate of every attempt drawn from `table` (dgll_hip_alias_build of this CSR's values): same
+ * counters, word 0 picks the slot, word 1 keeps it or takes its alias, word 2 is the acceptance word against T (used when p or
+ * q != 1 and s > 1), so P(x | t, v) is proportional to val(v, x) * w(t, x).  The first step is weighted as well.  Cap, capped
+ * count, dead ends and error bits as above; bit 8 of info[1]: an alias index outside its row (the table is not this graph's).  */
+int dgll_hip_random_walk_weighted(void* stream, const int64_t* rowptr, const int32_t* col, const uint32_t* table, int64_t n_nodes,
+                                  const int64_t* starts, int64_t n, int length, uint64_t first_walk_index, uint64_t seed, double p,
+                                  double q, int max_attempts, int32_t* walks, int64_t* info);
 /* Pairs of a batch of walks: centre = position j of walk w, context slot s in [0, 2 window) = position j + o, o = -window..-1,
  * 1..window; the pair exists when both positions lie in the walk and hold ids in [0, n_nodes).  Negative k of a pair is
  * searchsorted(cdf, x0, side = right) with cdf uint64[n_nodes] the noise distribution's cumulative sums scaled to 2^32

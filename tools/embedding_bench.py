@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Throughput of the embedding kernels on the products-shaped synthetic graph: walk steps/s (uniform and node2vec), skip-gram
+"""Throughput of the embedding kernels on the products-shaped synthetic graph: walk steps/s (uniform, node2vec, and both again
+edge-weighted through the alias table, whose build time is reported too), skip-gram
 pairs/s of one sgns_step at D = 128, L = 80, W = 5, K = 5, and the bytes/s the W_out pass adds atomically (every existing pair
 adds K rows for its negatives; the positives of a position are summed first and add one row).  Prints one JSON line.
 
@@ -52,6 +53,21 @@ def main():
         walks = embedding.random_walks(g, starts, L, p=p, q=q, seed=1)
         steps = int((walks[:, 1:] >= 0).sum())
         out["walk_steps_per_s_" + name] = steps / t
+    # edge weights 2^u, u uniform in [-2, 2): the table build (one lane per row, once per graph) and the same two walks through it
+    gw = g.with_values(torch.exp2(torch.rand(g.nnz, device=dev) * 4.0 - 2.0))
+
+    def build_table():
+        gw._alias = None
+        return embedding.AliasTable.from_graph(gw)
+
+    out["alias_build_s"] = timed(build_table, args.reps)                  # includes the blocking read of the info word
+    alias = embedding.AliasTable.from_graph(gw)
+    out["alias_table_bytes"] = alias.table.numel() * 4
+    for name, (p, q) in (("weighted", (1.0, 1.0)), ("weighted_node2vec_p0.5_q2", (0.5, 2.0))):
+        embedding.random_walks(gw, starts, 2, p=p, q=q, alias=alias)
+        t = timed(lambda: embedding.random_walks(gw, starts, L, p=p, q=q, seed=1, alias=alias), args.reps)
+        walks = embedding.random_walks(gw, starts, L, p=p, q=q, seed=1, alias=alias)
+        out["walk_steps_per_s_" + name] = int((walks[:, 1:] >= 0).sum()) / t
     walks = embedding.random_walks(g, starts, L, seed=1)
     noise = embedding.NoiseTable.from_graph(g)
     w_in = torch.rand((g.n_rows, D), device=dev)
