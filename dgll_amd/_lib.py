@@ -187,6 +187,10 @@ SIGNATURES = {
     "dgll_hip_alias_build": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),
     "dgll_hip_random_walk_weighted": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _i32,
                                              _vp, _vp]),
+    "dgll_hip_struc_dtw": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "dgll_hip_struc_dtw_max_rows": (_i32, []),
+    "dgll_hip_struc_walk": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, C.c_uint64, C.c_uint64, C.c_double, _i32, _vp, _vp,
+                                   _vp]),
     "dgll_hip_sgns_negatives": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, C.c_uint64, C.c_uint64, _vp]),
     "dgll_hip_sgns_step": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp, C.c_uint64, C.c_uint64, C.c_float,
                                   _vp, _vp, _vp, _vp]),

@@ -177,6 +177,71 @@ __global__ __launch_bounds__(kBlock) void random_walk_weighted_kernel(const int6
     if (capped) atomicAdd(info + kInfoCapped, capped);
 }
 
+// struc2vec's walk over the multilayer context graph: a stacked CSR of n_layers * n_nodes rows (row layer * n_nodes + v holds v's
+// neighbours in that layer, plain node ids) with its alias table.  The lane carries (v, layer), layer 0 at the start.  Attempt a of
+// step s draws one block: x0 < t_stay stays in the layer and emits a neighbour drawn from the row as random_walk_weighted_kernel
+// draws it (x1 the slot, x2 keep or alias); otherwise x3 < t_up[row] moves up when row (layer + 1) * n_nodes + v has entries, and
+// down when it is not an up-move and layer > 0 -- no node is emitted and the next attempt follows.  The last allowed attempt stays
+// whatever x0 says and is counted.  The same pointer chasing as above with one more level (t_up) on a layer move.
+__global__ __launch_bounds__(kBlock) void struc_walk_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                            const uint2* __restrict__ table, const uint32_t* __restrict__ t_up,
+                                                            int64_t n_nodes, int n_layers, const int64_t* __restrict__ starts, int64_t n,
+                                                            int length, uint64_t first, uint64_t seed, uint64_t t_stay, int max_attempts,
+                                                            int32_t* __restrict__ walks, int32_t* __restrict__ layers_out,
+                                                            unsigned long long* __restrict__ info) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t widx = first + (uint64_t)i;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    int32_t* out = walks + i * length;
+    int32_t* lay = layers_out ? layers_out + i * length : nullptr;
+    const int64_t s0 = starts[i];
+    int32_t v = (int32_t)s0;
+    int layer = 0;
+    if (s0 < 0 || s0 >= n_nodes) { v = -1; atomicOr(info + kInfoErr, (unsigned long long)kErrStart); }
+    out[0] = v;
+    if (lay) lay[0] = v >= 0 ? 0 : -1;
+    unsigned long long capped = 0;
+    for (int s = 1; s < length; ++s) {
+        int32_t next = -1;
+        if (v >= 0) {
+            for (int a = 0; a < max_attempts; ++a) {
+                const uint32_t ctr[4] = {(uint32_t)widx, (uint32_t)(widx >> 32), (uint32_t)s, (uint32_t)a};
+                uint32_t x[4];
+                philox4x32_10(ctr, key, x);
+                const int64_t row = (int64_t)layer * n_nodes + v;
+                const bool last = a == max_attempts - 1;
+                if (last) ++capped;                                          // the cap: this attempt stays, and says so
+                if ((uint64_t)x[0] < t_stay || last) {
+                    const int64_t b = rowptr[row];
+                    const uint32_t deg = (uint32_t)(rowptr[row + 1] - b);    // < 2^32: checked on the host
+                    if (deg == 0u) break;                                    // nobody to go to in this layer: the walk ends
+                    const uint32_t slot = __umulhi(x[1], deg);
+                    const uint2 ta = table[b + (int64_t)slot];
+                    if (ta.x == 0u && ta.y == slot) break;                   // the row's weights sum to 0: a dead end
+                    const uint32_t e = x[2] < ta.x ? slot : ta.y;
+                    if (e >= deg) { atomicOr(info + kInfoErr, (unsigned long long)kErrAlias); break; }
+                    next = col[b + (int64_t)e];
+                    if (next < 0 || next >= n_nodes) { next = -1; atomicOr(info + kInfoErr, (unsigned long long)kErrCol); }
+                    break;
+                }
+                if (x[3] < t_up[row]) {
+                    if (layer + 1 < n_layers) {
+                        const int64_t above = row + n_nodes;
+                        if (rowptr[above + 1] > rowptr[above]) ++layer;
+                    }
+                } else if (layer > 0) {
+                    --layer;
+                }
+            }
+        }
+        v = next;
+        out[s] = v;
+        if (lay) lay[s] = v >= 0 ? layer : -1;
+    }
+    if (capped) atomicAdd(info + kInfoCapped, capped);
+}
+
 }  // namespace walk
 }  // namespace dgll
 
@@ -243,6 +308,25 @@ DGLL_API int dgll_hip_random_walk_weighted(void* stream, const int64_t* rowptr, 
     hipLaunchKernelGGL(walk::random_walk_weighted_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        static_cast<hipStream_t>(stream), rowptr, col, reinterpret_cast<const uint2*>(table), n_nodes, starts, n, length,
                        first_walk_index, seed, T[0], T[1], T[2], biased, max_attempts, walks, reinterpret_cast<unsigned long long*>(info));
+    DGLL_HIP_TRY(hipGetLastError());
+    return DGLL_OK;
+}
+
+DGLL_API int dgll_hip_struc_walk(void* stream, const int64_t* rowptr, const int32_t* col, const uint32_t* table, const uint32_t* t_up,
+                                 int64_t n_nodes, int n_layers, const int64_t* starts, int64_t n, int length, uint64_t first_walk_index,
+                                 uint64_t seed, double stay_prob, int max_attempts, int32_t* walks, int32_t* layers_out, int64_t* info) {
+    DGLL_REQUIRE(rowptr && (starts || n == 0) && (walks || n == 0) && info && t_up, "CSR, t_up, starts, walks and info must be non-NULL");
+    DGLL_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7u) == 0, "the alias table must be 8-byte aligned");
+    DGLL_REQUIRE(length >= 1, "walk length must be >= 1");
+    DGLL_REQUIRE(stay_prob >= 0.0 && stay_prob <= 1.0, "stay_prob must lie in [0, 1]");
+    DGLL_REQUIRE(n >= 0 && n_nodes > 0 && n_nodes < (1ll << 31) && n <= (1ll << 31) * kBlock - kBlock, "walk count, node count < 2^31");
+    DGLL_REQUIRE(n_layers >= 1 && max_attempts >= 1, "n_layers and the attempt cap must be >= 1");
+    if (n == 0) return DGLL_OK;
+    const uint64_t t_stay = (uint64_t)rint(4294967296.0 * stay_prob);
+    hipLaunchKernelGGL(walk::struc_walk_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), rowptr, col, reinterpret_cast<const uint2*>(table), t_up, n_nodes, n_layers,
+                       starts, n, length, first_walk_index, seed, t_stay, max_attempts, walks, layers_out,
+                       reinterpret_cast<unsigned long long*>(info));
     DGLL_HIP_TRY(hipGetLastError());
     return DGLL_OK;
 }

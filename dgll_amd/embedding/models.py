@@ -8,6 +8,7 @@ import torch.nn as nn
 
 from ..graph import CSRGraph
 from .sgns import NoiseTable, sgns_step
+from .struc2vec import StrucContext, struc_walks
 from .walks import AliasTable, as_walk_graph, random_walks, walk_info
 
 
@@ -182,6 +183,33 @@ class DeepWalk(RandomWalkEmbedding):
             warnings.warn("Provide a graph: {}".format(graph))
             sys.exit()
         super().__init__(graph, walkLength, embedDim, numbOfWalksPerVertex, windowSize, lr, **kw)
+
+
+class Struc2Vec(RandomWalkEmbedding):
+    """struc2vec.py:22-61: walks over the multilayer context graph of structural similarity (StrucContext, built here, once, on the
+    device); stay_prob == 0 selects 0.3.  temp_path and reuse are accepted and ignored: nothing is pickled to disk.  The noise
+    table of the negative draws stays in-degree^0.75 of the input graph."""
+
+    def __init__(self, graph=None, walkLength=0, embedDim=0, numbOfWalksPerVertex=0, windowSize=0, lr=0, verbose=0, stay_prob=0,
+                 opt1_reduce_len=True, opt2_reduce_sim_calc=True, opt3_num_layers=None, temp_path=None, reuse=False, **kw):
+        if graph is None:
+            warnings.warn("Provide a graph: {}".format(graph))
+            sys.exit()
+        super().__init__(graph, walkLength, embedDim, numbOfWalksPerVertex, windowSize, lr, **kw)
+        if stay_prob == 0:
+            self.stay_prob = 0.3
+            warnings.warn("Set stay prob. to default: {}".format(self.stay_prob))
+        else:
+            self.stay_prob = stay_prob
+        self.verbose = verbose
+        self.opt1_reduce_len, self.opt2_reduce_sim_calc, self.opt3_num_layers = opt1_reduce_len, opt2_reduce_sim_calc, opt3_num_layers
+        self.context = StrucContext.from_graph(self.csr, opt1_reduce_len, opt2_reduce_sim_calc, opt3_num_layers)
+
+    def _walk_batch(self, starts, length, info=None):
+        walks = struc_walks(self.context, starts, length, self.stay_prob, self.seed, self._walks_drawn, info=info)
+        first = self._walks_drawn
+        self._walks_drawn += int(starts.numel())
+        return walks, first
 
 
 class Node2vec(RandomWalkEmbedding):

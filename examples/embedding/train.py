@@ -5,6 +5,8 @@ device (dgll_amd.embedding).  Prints the loss of every epoch and the mean cosine
     python examples/embedding/train.py --method deepwalk
     python examples/embedding/train.py --method node2vec --p 0.5 --q 2 --communities 8 --nodes 4000 --dim 64
     python examples/embedding/train.py --method node2vec --weighted      # edges inside a community weigh 4, the others 1
+    python examples/embedding/train.py --method struc2vec --stay-prob 0.3 --num-layers 3 --lr 0.0005
+                                       # structural roles, not communities: the intra/inter split is only printed for comparison
 """
 import argparse
 import os
@@ -45,7 +47,7 @@ def cosine_split(emb, comm, sample=2000, seed=0):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--method", choices=["deepwalk", "node2vec"], default="deepwalk")
+    ap.add_argument("--method", choices=["deepwalk", "node2vec", "struc2vec"], default="deepwalk")
     ap.add_argument("--nodes", type=int, default=2000)
     ap.add_argument("--communities", type=int, default=4)
     ap.add_argument("--dim", type=int, default=64)
@@ -59,6 +61,8 @@ def main():
     ap.add_argument("--q", type=float, default=2.0)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--stay-prob", type=float, default=0.3, help="struc2vec: probability of staying in the layer")
+    ap.add_argument("--num-layers", type=int, default=3, help="struc2vec: opt3_num_layers (BFS levels 0..K); -1 = unbounded")
     ap.add_argument("--weighted", action="store_true", help="walk in proportion to edge weights (4 inside a community, 1 across)")
     args = ap.parse_args()
 
@@ -69,7 +73,13 @@ def main():
         same = torch.from_numpy(comm)[g.row_index().cpu()] == torch.from_numpy(comm)[g.col.cpu().long()]
         g = g.with_values(torch.where(same, 4.0, 1.0).to(dev))
     kw = dict(negatives=args.negatives, batch_walks=args.batch_walks, seed=args.seed, weighted=args.weighted)
-    if args.method == "deepwalk":
+    if args.method == "struc2vec":
+        kw.pop("weighted")
+        emb = embedding.Struc2Vec(g, args.walk_length, args.dim, args.walks_per_vertex, args.window, args.lr, stay_prob=args.stay_prob,
+                                  opt3_num_layers=None if args.num_layers < 0 else args.num_layers, **kw)
+        print("context graph: %d layers, %d pairs, build seconds %s" % (emb.context.n_layers, emb.context.pairs.shape[0],
+                                                                        {k: round(v, 4) for k, v in emb.context.timings.items()}))
+    elif args.method == "deepwalk":
         emb = embedding.DeepWalk(g, args.walk_length, args.dim, args.walks_per_vertex, args.window, args.lr, **kw)
     else:
         emb = embedding.Node2vec(g, args.walk_length, args.dim, args.walks_per_vertex, args.window, args.lr, args.p, args.q, **kw)

@@ -713,6 +713,30 @@ int dgll_hip_alias_build(void* stream, const int64_t* rowptr, const float* val, 
 int dgll_hip_random_walk_weighted(void* stream, const int64_t* rowptr, const int32_t* col, const uint32_t* table, int64_t n_nodes,
                                   const int64_t* starts, int64_t n, int length, uint64_t first_walk_index, uint64_t seed, double p,
                                   double q, int max_attempts, int32_t* walks, int64_t* info);
+/* struc2vec, structural distances: exact dynamic time warping between ordered degree sequences, one task per (pair, level).
+ * Sequences are ragged: the sequence of node v at BFS level l is entries [seq_ptr[v * n_levels + l], seq_ptr[v * n_levels + l + 1])
+ * of seq_deg / seq_cnt (int32: a degree and how many nodes of the ring have it, degrees ascending; counts >= 1), seq_ptr
+ * int64[n_nodes * n_levels + 1].  pairs: int32[n_pairs, 2] node ids in [0, n_nodes).  dist: fp64[n_pairs, n_levels] row-major,
+ * D[i][j] = c + min(D[i-1][j], D[i][j-1], D[i-1][j-1]), c = ((max(da, db) + 0.5) / (min(da, db) + 0.5) - 1) * max(ca, cb), in IEEE
+ * float64 without contraction; d(a, b) and d(b, a) are the same bits.  -1 from the first level at which either node's sequence is
+ * empty.  The shorter sequence of a task may hold at most dgll_hip_struc_dtw_max_rows() entries (a task over it is written as NaN;
+ * callers check beforehand).                                                                                                    */
+int dgll_hip_struc_dtw(void* stream, const int64_t* seq_ptr, const int32_t* seq_deg, const int32_t* seq_cnt, int64_t n_nodes,
+                       int n_levels, const int32_t* pairs, int64_t n_pairs, double* dist);
+int dgll_hip_struc_dtw_max_rows(void);
+/* struc2vec, the walk over the multilayer context graph: a stacked CSR of n_layers * n_nodes rows, row l * n_nodes + v = the
+ * neighbours of v in layer l (int64 rowptr[n_layers * n_nodes + 1], int32 col holding node ids in [0, n_nodes)), `table` its
+ * dgll_hip_alias_build table, t_up uint32[n_layers * n_nodes] the up-move thresholds round(2^32 x / (x + 1)), x = log(gamma + e).
+ * A walk holds (v, layer), layer 0 at its start.  Step s >= 1 runs attempts a = 0, 1, ... with the counter {g lo, g hi, s, a}:
+ * x0 < T_stay = round(2^32 stay_prob): stay -- slot = mulhi32(x1, deg), edge = x2 < T[slot] ? slot : alias[slot], the column is
+ * emitted and the step ends; an empty or dead row ends the walk (-1 from there on).  Otherwise x3 < t_up[row]: up one layer when
+ * layer + 1 < n_layers and row (layer + 1) * n_nodes + v has entries; else down one layer when layer > 0.  Attempt
+ * max_attempts - 1 (max_attempts >= 1) stays whatever x0 says; every time it is reached info[0] is incremented.  walks
+ * int32[n, length]; layers_out: NULL or int32[n, length], the layer every entry was emitted from (0 for the start, -1 where the
+ * walk is -1).  info and its error bits as for dgll_hip_random_walk_weighted.                                                   */
+int dgll_hip_struc_walk(void* stream, const int64_t* rowptr, const int32_t* col, const uint32_t* table, const uint32_t* t_up,
+                        int64_t n_nodes, int n_layers, const int64_t* starts, int64_t n, int length, uint64_t first_walk_index,
+                        uint64_t seed, double stay_prob, int max_attempts, int32_t* walks, int32_t* layers_out, int64_t* info);
 /* Pairs of a batch of walks: centre = position j of walk w, context slot s in [0, 2 window) = position j + o, o = -window..-1,
  * 1..window; the pair exists when both positions lie in the walk and hold ids in [0, n_nodes).  Negative k of a pair is
  * searchsorted(cdf, x0, side = right) with cdf uint64[n_nodes] the noise distribution's cumulative sums scaled to 2^32

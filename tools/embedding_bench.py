@@ -2,7 +2,9 @@
 """Throughput of the embedding kernels on the products-shaped synthetic graph: walk steps/s (uniform, node2vec, and both again
 edge-weighted through the alias table, whose build time is reported too), skip-gram
 pairs/s of one sgns_step at D = 128, L = 80, W = 5, K = 5, and the bytes/s the W_out pass adds atomically (every existing pair
-adds K rows for its negatives; the positives of a position are summed first and add one row).  Prints one JSON line.
+adds K rows for its negatives; the positives of a position are summed first and add one row); and struc2vec on a smaller graph
+of the same shape (--struc-nodes, stated in the output): the context build split into BFS, pairs, DTW, graph and alias seconds,
+DTW tasks/s and cells/s, and the multilayer walk's steps/s.  Prints one JSON line.
 
     python tools/embedding_bench.py [--nodes N] [--walks 4096] [--reps 5]
 """
@@ -31,6 +33,29 @@ def timed(fn, reps):
     return best
 
 
+def struc2vec_section(dev, args):
+    """Context build (opt1 and opt2 on) and multilayer walk on a products-shaped graph of --struc-nodes nodes."""
+    from dgll_amd.embedding import struc2vec as s2v
+
+    sn = args.struc_nodes
+    g = synth.products_like_graph(dev, n=sn, n_undirected=max(sn, int(args.edges * (sn / args.nodes))))
+    s2v.StrucContext.from_graph(g, True, True, args.struc_layers)             # warm-up: allocator, SpMM plan
+    ctx = s2v.StrucContext.from_graph(g, True, True, args.struc_layers)
+    res = {"nodes": g.n_rows, "nnz": g.nnz, "levels": ctx.n_layers, "pairs": int(ctx.pairs.shape[0]), "stacked_edges": ctx.graph.nnz,
+           "build_s": {k: v for k, v in ctx.timings.items()}}
+    lens = ctx.seqs.lengths()
+    pl = ctx.pairs.to(torch.int64)
+    valid = ctx.dist >= 0
+    cells = int((lens[pl[:, 0]] * lens[pl[:, 1]])[valid].sum())
+    t = timed(lambda: s2v.struc_dtw(ctx.seqs, ctx.pairs), args.reps)            # includes the length check's blocking read
+    res.update(dtw_s=t, dtw_tasks_per_s=int(valid.sum()) / t, dtw_cells_per_s=cells / t, dtw_mean_cells_per_task=cells / max(int(valid.sum()), 1))
+    starts = torch.randint(0, g.n_rows, (args.walks,), device=dev)
+    t = timed(lambda: s2v.struc_walks(ctx, starts, args.length, 0.3, 1, 0), args.reps)
+    walks = s2v.struc_walks(ctx, starts, args.length, 0.3, 1, 0)
+    res["walk_steps_per_s"] = int((walks[:, 1:] >= 0).sum()) / t
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=synth.PRODUCTS_NODES)
@@ -41,6 +66,8 @@ def main():
     ap.add_argument("--window", type=int, default=5)
     ap.add_argument("--negatives", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--struc-nodes", type=int, default=20000, help="struc2vec section: nodes of its graph (0 skips the section)")
+    ap.add_argument("--struc-layers", type=int, default=3, help="struc2vec section: opt3_num_layers")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     g = synth.products_like_graph(dev, n=args.nodes, n_undirected=args.edges)
@@ -82,6 +109,8 @@ def main():
     atomic_bytes = (pairs * K + positions) * D * 4
     out["w_out_atomic_bytes_per_step"] = atomic_bytes
     out["w_out_atomic_bytes_per_s_over_whole_step"] = atomic_bytes / t
+    if args.struc_nodes:
+        out["struc2vec"] = struc2vec_section(dev, args)
     print(json.dumps(out))
 
 
