@@ -1,5 +1,5 @@
 """Drop-in `dgll` namespace: the reference's import paths (`from dgll import backend as F`,
-`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.dataloader`, `dgll.embedding`) resolved onto
+`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.dataloader`, `dgll.embedding`, `dgll.community`) resolved onto
 the MI355X-native implementation in dgll_amd.  /root/reference/dgll/__init__.py:1 is `import torch as backend`;
 here `backend` is dgll_amd.backend (torch + the missing aliases + HIP aggregation)."""
 import importlib
@@ -25,11 +25,14 @@ _ALIASES = {
     "dgll.sampling.base_sampler": "dgll_amd.sampling.base_sampler",
     "dgll.sampling.dgllsampler": "dgll_amd.sampling.dgllsampler",
     "dgll.sampling.layerwise": "dgll_amd.sampling.layerwise",
+    "dgll.sampling.community": "dgll_amd.sampling.community",
     "dgll.dataloader": "dgll_amd.dataloader",
     "dgll.embedding": "dgll_amd.embedding",
+    "dgll.community": "dgll_amd.community",
 }
 for _alias, _target in _ALIASES.items():
     sys.modules[_alias] = importlib.import_module(_target)
 nn = sys.modules["dgll.nn"]
+community = sys.modules["dgll.community"]
 embedding = sys.modules["dgll.embedding"]      # `import dgll.embedding` finds the alias in sys.modules and binds no attribute itself
 __version__ = dgll_amd.__version__

@@ -8,5 +8,6 @@ from . import _lib  # noqa: F401  (must succeed: no CPU fallback for CUDA tensor
 from .graph import CSRGraph  # noqa: F401
 from . import ops  # noqa: F401
 from . import backend  # noqa: F401
+from . import community  # noqa: F401  (CoG: size-capped Louvain communities, groups, CommunityBook)
 
 __version__ = "0.1.0"

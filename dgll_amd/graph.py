@@ -196,10 +196,11 @@ class CSRGraph:
     perm = None        # set on a graph returned by reorder(): row i of this graph is row perm[i] of the caller's graph
     inv_perm = None    # and caller node v is row inv_perm[v] here
 
-    def reorder(self, method="lpa", seed=0, sweeps=8):
+    def reorder(self, method="lpa", seed=0, sweeps=8, max_comm_size=None):
         """(relabelled CSRGraph, perm): the engine's one-off locality pass (dgll_amd/reorder.py) -- community relabelling
         computed on the device the graph lives on.  Permute node data once with `x[perm]` (`to_engine_order`); results come
-        back in the caller's node order through `to_caller_order`."""
+        back in the caller's node order through `to_caller_order`.  method="louvain" (GPU only) orders by size-capped modularity
+        communities, max_comm_size nodes at the most (dgll_amd/community.py)."""
         from . import reorder as _reorder
 
         if self.n_rows != self.n_cols:
@@ -208,7 +209,8 @@ class CSRGraph:
             method = "degree"         # label propagation sorts the edge list in one call; beyond 2^30 edges: hubs first (what
                                       # "lpa" degenerates to on a structure-free graph).  RMAT-25 / 27, F = 128 bf16, final
                                       # round-2 kernels: hubs-first 86 / 86 %, random 67 / 70 %, generator ids 41 / 53 % of 8 TB/s
-        perm = _reorder.locality_order(self.rowptr, self.col, self.n_rows, method=method, seed=seed, sweeps=sweeps)
+        perm = _reorder.locality_order(self.rowptr, self.col, self.n_rows, method=method, seed=seed, sweeps=sweeps,
+                                       max_comm_size=max_comm_size)
         return _reorder.relabel(self, perm), perm
 
     def to_engine_order(self, x):

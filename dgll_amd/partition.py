@@ -188,8 +188,9 @@ def partition_and_order(graph, n_parts, seed=0, sweeps=8, refine=True, imbalance
     return order, [0] + torch.cumsum(counts, 0).tolist()
 
 
-def community_parts(graph, n_parts, seed=0, sweeps=8, return_communities=False):
-    """node -> part for a square CSRGraph: communities found by label propagation, packed largest-first into the part
+def community_parts(graph, n_parts, seed=0, sweeps=8, return_communities=False, method="lpa", max_comm_size=None):
+    """node -> part for a square CSRGraph: communities found by label propagation (method="louvain": by dgll_amd.community.louvain,
+    GPU only, at most max_comm_size nodes each), packed largest-first into the part
     with the fewest edges so far (longest-processing-time bin packing on the communities' edge counts).  Communities larger
     than a fair share are split by node order so that no part exceeds it by more than one community's worth."""
     from . import reorder
@@ -197,7 +198,14 @@ def community_parts(graph, n_parts, seed=0, sweeps=8, return_communities=False):
     if graph.n_rows != graph.n_cols:
         raise ValueError("partitioning needs a square adjacency")
     n = graph.n_rows
-    labels = reorder.label_propagation(graph.rowptr, graph.col, n, sweeps=sweeps, seed=seed)
+    if method == "louvain":
+        from . import community
+
+        labels = community.louvain(graph, max_comm_size=max_comm_size, seed=seed)
+    elif method == "lpa":
+        labels = reorder.label_propagation(graph.rowptr, graph.col, n, sweeps=sweeps, seed=seed)
+    else:
+        raise ValueError("community_parts method must be 'lpa' or 'louvain'")
     _, dense, size = torch.unique(labels, return_inverse=True, return_counts=True)
     rank = torch.empty_like(size)                    # communities numbered largest first (as reorder.locality_order)
     rank[torch.argsort(size, descending=True, stable=True)] = torch.arange(size.numel(), device=size.device)

@@ -56,10 +56,11 @@ def label_propagation(rowptr, col, n, sweeps=8, seed=0):
     return labels
 
 
-def locality_order(rowptr, col, n, method="lpa", seed=0, sweeps=8):
-    """perm (int64 [n]): the node that becomes row i of the reordered graph."""
-    if method not in ("lpa", "degree", "random"):
-        raise ValueError("reorder method must be 'lpa', 'degree' or 'random'")
+def locality_order(rowptr, col, n, method="lpa", seed=0, sweeps=8, max_comm_size=None):
+    """perm (int64 [n]): the node that becomes row i of the reordered graph.  method="louvain": size-capped modularity communities
+    (dgll_amd/community.py, GPU only; max_comm_size=None leaves them uncapped) in place of label propagation's."""
+    if method not in ("lpa", "louvain", "degree", "random"):
+        raise ValueError("reorder method must be 'lpa', 'louvain', 'degree' or 'random'")
     deg = rowptr[1:] - rowptr[:-1]
     dmax = int(deg.max()) + 1 if n else 1
     ids = torch.arange(n, device=rowptr.device)
@@ -70,7 +71,13 @@ def locality_order(rowptr, col, n, method="lpa", seed=0, sweeps=8):
     if method == "degree":          # hubs first (what "lpa" degenerates to when the graph is one community)
         key = (dmax - 1 - deg) * n + ids
     else:
-        labels = label_propagation(rowptr, col, n, sweeps=sweeps, seed=seed)
+        if method == "louvain":
+            from . import community
+            from .graph import CSRGraph
+
+            labels = community.louvain(CSRGraph(rowptr, col, None, n, n, check=False), max_comm_size=max_comm_size, seed=seed)
+        else:
+            labels = label_propagation(rowptr, col, n, sweeps=sweeps, seed=seed)
         # communities largest first (the dust of isolated nodes and tiny components goes to the end); inside a community
         # hubs first, then old id (deterministic)
         _, dense_label, size = torch.unique(labels, return_inverse=True, return_counts=True)

@@ -752,6 +752,30 @@ int dgll_hip_sgns_negatives(void* stream, const int32_t* walks, int64_t n, int l
 int dgll_hip_sgns_step(void* stream, float* w_in, float* w_out, int64_t n_nodes, int dim, const int32_t* walks, int64_t n, int length,
                        int window, int negatives, const uint64_t* cdf, uint64_t first_walk_index, uint64_t seed, float lr,
                        float* g_scratch, int32_t* target_scratch, float* delta_scratch, double* loss);
+/* Size-capped Louvain, one synchronous local-moving sweep of one level (dgll_amd/community.py runs the levels).  CSR rowptr int64
+ * [n + 1], col int32 [nnz]; w: int64 [nnz] entry weights, NULL = 1 per stored entry; k int64 [n] weighted degree (self-loop entries
+ * included); size int64 [n] original nodes per node; comm int32 [n] in [0, n); tot / csize int64 [n] and cnt int32 [n]: per
+ * community the sum of k, of size and the member count, as they are at the start of the sweep; two_m = sum(k), in [1, 2^53).
+ * Node v of community a is active when all_active != 0 or bit 0 of word 0 of Philox4x32-10 with key {seed lo, seed hi} and counter
+ * {v, level, sweep, 0} is set.  With W(v, x) the summed weight of v's entries (v, u), u != v, comm[u] == x:
+ *     gain(c) = (double)W(v, c) - resolution * (double)k_v * (double)tot_c / (double)two_m
+ *     stay    = (double)W(v, a) - resolution * (double)k_v * (double)(tot_a - k_v) / (double)two_m
+ * evaluated left to right in IEEE float64 without contraction.  target[v] = the community c != a among v's neighbours with
+ * csize_c + size_v <= cap, gain(c) > stay and not (cnt_a == 1 && cnt_c == 1 && c > a) that has the largest gain, ties to the
+ * smallest id; a for an inactive node or when there is none.  W is summed with integer atomics in hash tables of
+ * 2 * next_pow2(deg) slots: in a wavefront's LDS for rows of up to wave_max_deg entries (<= 128, -1 = 128), in a workgroup's LDS up
+ * to block_max_deg (<= 2048, -1 = 2048), in `scratch` beyond; the three give the same targets.
+ * scratch: 8-byte aligned, dgll_hip_louvain_scratch_bytes(n, long_slots) bytes = 64 + 4 n + 12 long_slots (the 4-byte part padded
+ * to 8), long_slots >= the sum of 2 * next_pow2(deg) over the active rows longer than block_max_deg; cleared here.
+ * info: int64[2], zeroed by the caller: info[0] += nodes whose target differs from their community; info[1] |= error bits (1: a
+ * column id outside [0, n), the entry is skipped; 2: scratch too small, the row keeps its community; 4: a row with 2^30 or more
+ * entries or row pointers outside [0, nnz]; 8: a community id outside [0, n)).                                                  */
+int dgll_hip_louvain_move(void* stream, const int64_t* rowptr, const int32_t* col, const int64_t* w, const int64_t* k,
+                          const int64_t* size, const int32_t* comm, const int64_t* tot, const int64_t* csize, const int32_t* cnt,
+                          int64_t n, int64_t nnz, int64_t two_m, double resolution, int64_t cap, uint64_t seed, uint32_t level,
+                          uint32_t sweep, int all_active, int wave_max_deg, int block_max_deg, void* scratch, size_t scratch_bytes,
+                          int32_t* target, int64_t* info);
+size_t dgll_hip_louvain_scratch_bytes(int64_t n, int64_t long_slots);
 
 
 /* ---- a10: H = relu(A_csr . (X[:, :actual_F] . W[:actual_F, :])) --------------------------------------------

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Size-capped Louvain (dgll_amd/community.py, csrc/louvain.hip) on the products-shaped graph, next to label propagation:
+
+  * seconds per level-0 sweep (one dgll_hip_louvain_move call with its scratch allocation and info read) and edges/s;
+  * the levels: nodes, sweeps, seconds;
+  * total seconds and modularity of `louvain` and of `reorder.label_propagation` on the same graph;
+  * the time of bench.py's SpMM shapes (bf16, mean, F = 100 / 256 / 47) on the graph ordered each way.
+
+    python tools/cog_bench.py [--nodes N] [--max-comm-size C]
+
+Prints one JSON line.  DESIGN.md section 6.3 says "Measured: not yet" until a run of this is recorded there.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from dgll_amd import community, ops, reorder, synth  # noqa: E402
+
+
+def timed(fn, reps=1):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out = fn()
+    torch.cuda.synchronize()
+    return out, (time.perf_counter() - t0) / reps
+
+
+def sweep_seconds(g, cap, reps=5):
+    """Level 0, sweep 0 (every node a singleton, the densest sweep): one move_targets call between two events."""
+    n, dev = g.n_rows, g.device
+    k, size = g.degrees().contiguous(), torch.ones(n, dtype=torch.int64, device=dev)
+    comm = torch.arange(n, dtype=torch.int32, device=dev)
+    tot, csize, cnt = community.community_state(k, size, comm, n)
+    args = (g.rowptr, g.col, None, k, size, comm, tot, csize, cnt, g.nnz, 1.0, cap, 0, 0, 0, False)
+    community.move_targets(*args)
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        community.move_targets(*args)                 # includes its scratch allocation and the blocking info read
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b) / 1e3)
+    return sorted(times)[len(times) // 2]
+
+
+def spmm_ms(g, widths=(100, 256, 47), reps=10):
+    out = {}
+    for f in widths:
+        x = ops.alloc_features(g.n_rows, f, torch.bfloat16, g.device, pad_to=64)
+        x.normal_()
+        ops.spmm(g, x, reduce="mean")
+        _, sec = timed(lambda: ops.spmm(g, x, reduce="mean"), reps)
+        out["F%d" % f] = round(sec * 1e3, 3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=synth.PRODUCTS_NODES)
+    ap.add_argument("--avg-degree", type=float, default=50.5)
+    ap.add_argument("--max-comm-size", type=int, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("cog_bench runs the HIP kernels: a GPU is required")
+    dev = torch.device("cuda:0")
+    g = synth.products_like_graph(dev, seed=0, n=args.nodes, n_undirected=int(args.nodes * args.avg_degree / 2), locality=0.9,
+                                  permute_ids=True)
+    cap = g.n_rows if args.max_comm_size is None else args.max_comm_size
+    rec = {"nodes": g.n_rows, "entries": g.nnz, "max_comm_size": cap, "max_degree": int(g.degrees().max())}
+    sec = sweep_seconds(g, cap)
+    rec["level0_sweep_s"], rec["level0_edges_per_s"] = round(sec, 6), round(g.nnz / sec)
+    levels, clock = [], [time.perf_counter()]
+
+    def on_sweep(level, sweep, comm, size):
+        if level == len(levels):
+            levels.append({"nodes": int(comm.numel()), "sweeps": 0, "s": 0.0})
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        levels[level]["sweeps"] += 1
+        levels[level]["s"] = round(levels[level]["s"] + now - clock[0], 4)       # includes the aggregation that built the level
+        clock[0] = now
+
+    labels, rec["louvain_s"] = timed(lambda: community.louvain(g, max_comm_size=args.max_comm_size, seed=args.seed, on_sweep=on_sweep))
+    rec["levels"] = levels
+    rec["louvain_communities"], rec["louvain_largest"] = int(labels.max()) + 1, int(torch.bincount(labels).max())
+    rec["louvain_modularity"] = round(community.modularity(g, labels), 5)
+    lpa, rec["lpa_s"] = timed(lambda: reorder.label_propagation(g.rowptr, g.col, g.n_rows, seed=args.seed))
+    dense = torch.unique(lpa, return_inverse=True)[1]
+    rec["lpa_communities"], rec["lpa_largest"] = int(dense.max()) + 1, int(torch.bincount(dense).max())
+    rec["lpa_modularity"] = round(community.modularity(g, dense), 5)
+    rec["spmm_ms"] = {"given_order": spmm_ms(g)}
+    for method in ("lpa", "louvain"):
+        g2, _ = g.reorder(method=method, seed=args.seed, max_comm_size=args.max_comm_size)
+        rec["spmm_ms"][method] = spmm_ms(g2)
+        del g2
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
