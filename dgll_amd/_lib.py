@@ -197,6 +197,7 @@ SIGNATURES = {
     "dgll_hip_louvain_move": (_i32, [_vp] * 10 + [_i64, _i64, _i64, C.c_double, _i64, C.c_uint64, C.c_uint32, C.c_uint32, _i32, _i32, _i32,
                                      _vp, _sz, _vp, _vp]),
     "dgll_hip_louvain_scratch_bytes": (_sz, [_i64, _i64]),
+    "dgll_hip_leiden_refine": (_i32, [_vp] * 12 + [_i64, _i64, _i64, C.c_double, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dgll_hip_gat_fwd_dropout": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32,
                                         C.c_float, _i32, _vp, _sz, C.c_double, _vp]),
     "dgll_hip_gat_bwd_rows_dropout": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64,

@@ -13,9 +13,15 @@ the host).
   * `tot`, `csize`, `cnt` are recomputed with integer index_add_, the coarse graph with a sort and segment sums: two runs with one
     seed give the same labels, and tests/louvain_ref.py restates the whole scheme in numpy with the same bits.
 
-Differences from the reference: Louvain local moving, not Leiden (no refinement phase); synchronous
-half-sweeps; a conservative cap; structure-only weights (every stored entry counts 1, `val` is ignored, as the reference builds its
-igraph from the edge list).
+`leiden` is what the reference calls: after the local moving of a level, a refinement phase splits every community into connected,
+well-connected sub-communities (synchronous sweeps in which only singletons move and a sub-community that is somebody's target
+keeps its members; `dgll_hip_leiden_refine` in the same file), the level is aggregated on the sub-communities, and the next level
+starts from the communities carried onto them.  Every community it returns is connected; `louvain`'s may fall into pieces.
+tests/leiden_ref.py restates it with the same bits.
+
+Differences from the reference: the refinement merges greedily (largest gain, ties to the smallest id)
+where leidenalg draws at random, and `louvain` has no refinement at all; synchronous half-sweeps; a conservative cap;
+structure-only weights (every stored entry counts 1, `val` is ignored, as the reference builds its igraph from the edge list).
 """
 import torch
 
@@ -26,7 +32,7 @@ WAVE_MAX_DEG = 128       # rows up to this many entries: one wavefront, a 256-sl
 BLOCK_MAX_DEG = 2048     # up to this many: one workgroup, a 4096-slot LDS table; longer rows use the global scratch
 _LARGE_NNZ = 1 << 30
 _ERRORS = {1: "a column id outside [0, N)", 2: "the scratch table is too small", 4: "a row with 2^30 or more entries or bad row pointers",
-           8: "a community id outside [0, N)"}
+           8: "a community id outside [0, N)", 16: "a bound community id outside [0, N)"}
 
 
 def _square(graph):
@@ -64,11 +70,7 @@ def move_targets(rowptr, col, w, k, size, comm, tot, csize, cnt, two_m, resoluti
         raise ValueError("the total weight must lie in [1, 2^53): the modularity gains are exact float64 only below it")
     if int(cap) < 1:
         raise ValueError("max_comm_size must be >= 1")
-    deg = rowptr[1:] - rowptr[:-1]
-    long_deg = deg[deg > max(int(block_max_deg), int(wave_max_deg))]
-    long_slots = int((2 * _next_pow2(long_deg)).sum()) if long_deg.numel() else 0
-    nbytes = int(_lib.lib.dgll_hip_louvain_scratch_bytes(n, long_slots))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    scratch, nbytes = _scratch(rowptr, wave_max_deg, block_max_deg)
     target = torch.empty(n, dtype=torch.int32, device=dev)
     info = torch.zeros(2, dtype=torch.int64, device=dev)
     _lib.launch("dgll_hip_louvain_move", dev, rowptr.data_ptr(), _lib.ptr(col), _lib.ptr(w), k.data_ptr(), size.data_ptr(),
@@ -79,6 +81,43 @@ def move_targets(rowptr, col, w, k, size, comm, tot, csize, cnt, two_m, resoluti
     if err:
         raise ValueError("louvain: " + ", ".join(m for bit, m in _ERRORS.items() if err & bit))
     return (target, want) if return_info else target
+
+
+def _scratch(rowptr, wave_max_deg, block_max_deg):
+    """(int64 tensor, bytes): the sweep kernels' scratch, with tables for every row longer than the workgroup tier."""
+    n = rowptr.numel() - 1
+    deg = rowptr[1:] - rowptr[:-1]
+    long_deg = deg[deg > max(int(block_max_deg), int(wave_max_deg))]
+    long_slots = int((2 * _next_pow2(long_deg)).sum()) if long_deg.numel() else 0
+    nbytes = int(_lib.lib.dgll_hip_louvain_scratch_bytes(n, long_slots))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=rowptr.device), nbytes
+
+
+def refine_targets(rowptr, col, w, k, size, sub, bound, tot, csize, cnt, totP, two_m, resolution, cap, wave_max_deg=WAVE_MAX_DEG,
+                   block_max_deg=BLOCK_MAX_DEG, return_info=False):
+    """One sweep of dgll_hip_leiden_refine: (target int32 [n], wS, wC, cut int64 [n]) -- where every singleton of `sub` that is well
+    connected to its community in `bound` would go, every node's weight into its own sub-community and into its bound community,
+    and every sub-community's weight to the rest of its bound community.  Raises ValueError on the kernel's error bits."""
+    if not rowptr.is_cuda:
+        raise RuntimeError("dgll_amd.community runs on the GPU only (got a %s graph); there is no CPU fallback" % rowptr.device)
+    dev = rowptr.device
+    n = rowptr.numel() - 1
+    if not 0 < int(two_m) < 2 ** 53:
+        raise ValueError("the total weight must lie in [1, 2^53): the modularity gains are exact float64 only below it")
+    if int(cap) < 1:
+        raise ValueError("max_comm_size must be >= 1")
+    scratch, nbytes = _scratch(rowptr, wave_max_deg, block_max_deg)
+    target = torch.empty(n, dtype=torch.int32, device=dev)
+    wS, wC, cut = (torch.empty(n, dtype=torch.int64, device=dev) for _ in range(3))
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    _lib.launch("dgll_hip_leiden_refine", dev, rowptr.data_ptr(), _lib.ptr(col), _lib.ptr(w), k.data_ptr(), size.data_ptr(),
+                sub.data_ptr(), bound.data_ptr(), tot.data_ptr(), csize.data_ptr(), cnt.data_ptr(), totP.data_ptr(), n, int(col.numel()),
+                int(two_m), float(resolution), int(cap), int(wave_max_deg), int(block_max_deg), scratch.data_ptr(), nbytes,
+                target.data_ptr(), wS.data_ptr(), wC.data_ptr(), cut.data_ptr(), info.data_ptr())
+    want, err = info.cpu().tolist()           # the sweep's one blocking read
+    if err:
+        raise ValueError("leiden: " + ", ".join(m for bit, m in _ERRORS.items() if err & bit))
+    return (target, wS, wC, cut, want) if return_info else (target, wS, wC, cut)
 
 
 def admit(comm, target, size, csize, cap):
@@ -163,6 +202,85 @@ def louvain(graph, max_comm_size=None, resolution=1.0, seed=0, max_levels=10, ma
         rowptr, col, w = _aggregate(rowptr, col, w, dense, uniq.numel())
         k = torch.zeros(uniq.numel(), dtype=torch.int64, device=dev).index_add_(0, dense, k)
         size = torch.zeros(uniq.numel(), dtype=torch.int64, device=dev).index_add_(0, dense, size)
+    return labels
+
+
+def refine(rowptr, col, w, k, size, bound, two_m, resolution, cap, max_sweeps=32, level=0, on_refine=None,
+           wave_max_deg=WAVE_MAX_DEG, block_max_deg=BLOCK_MAX_DEG):
+    """int32 [n]: Leiden's sub-communities of a level, from singletons.  Sweeps until one admits nobody (at most max_sweeps): only
+    singletons move, a would-be mover that is itself somebody's target stays, then `admit` keeps the cap.  A sub-community's
+    members at the start of a sweep therefore never leave it and every joiner is adjacent to one of them: it stays connected."""
+    n = rowptr.numel() - 1
+    dev = rowptr.device
+    sub = torch.arange(n, dtype=torch.int32, device=dev)
+    totP = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, bound.long(), k)
+    for sweep in range(max_sweeps):
+        tot, csize, cnt = community_state(k, size, sub, n)
+        target, _, _, _, want = refine_targets(rowptr, col, w, k, size, sub, bound, tot, csize, cnt, totP, two_m, resolution, cap,
+                                               wave_max_deg, block_max_deg, return_info=True)
+        moved = 0
+        if want:
+            wants = target != sub
+            aimed = torch.zeros(n, dtype=torch.bool, device=dev)
+            aimed[target[wants].long()] = True
+            target = torch.where(wants & ~aimed[sub.long()], target, sub)
+            movers, t = admit(sub, target, size, csize, cap)
+            sub[movers] = t.to(torch.int32)
+            moved = movers.numel()
+        if on_refine is not None:
+            on_refine(level, sweep, sub, bound, size)
+        if moved == 0:
+            break
+    return sub
+
+
+def leiden(graph, max_comm_size=None, resolution=1.0, seed=0, max_levels=20, max_sweeps=32, on_sweep=None, on_refine=None):
+    """int64 [n] dense community labels of a square CSRGraph on the GPU: size-capped Leiden (module docstring); every community is
+    connected.  max_comm_size=None means n.  max_levels=20: a level shrinks the node count by the refinement's merges only (about
+    3x on the test graphs), and 3^20 exceeds the 2^31 nodes the kernels accept.  on_sweep(level, sweep, comm, size): after every
+    local-moving sweep's admission; on_refine(level, sweep, sub, bound, size): after every refinement sweep's."""
+    graph = _square(graph)
+    if not graph.is_cuda:
+        raise RuntimeError("dgll_amd.community runs on the GPU only (got a %s graph); there is no CPU fallback" % graph.device)
+    n = graph.n_rows
+    cap = n if max_comm_size is None else int(max_comm_size)
+    if cap < 1:
+        raise ValueError("max_comm_size must be >= 1")
+    if max_levels < 1 or max_sweeps < 1:
+        raise ValueError("max_levels and max_sweeps must be >= 1")
+    dev = graph.device
+    labels = torch.arange(n, dtype=torch.int64, device=dev)
+    if graph.nnz == 0 or n == 0:
+        return labels
+    rowptr, col, w = graph.rowptr, graph.col, None
+    k, size = graph.degrees().contiguous(), torch.ones(n, dtype=torch.int64, device=dev)
+    two_m = graph.nnz
+    comm = torch.arange(n, dtype=torch.int32, device=dev)
+    for level in range(max_levels):
+        nl = rowptr.numel() - 1
+        for sweep in range(max_sweeps):
+            tot, csize, cnt = community_state(k, size, comm, nl)
+            target = move_targets(rowptr, col, w, k, size, comm, tot, csize, cnt, two_m, resolution, cap, seed, level, sweep,
+                                  sweep == max_sweeps - 1)
+            movers, t = admit(comm, target, size, csize, cap)
+            comm[movers] = t.to(torch.int32)
+            if on_sweep is not None:
+                on_sweep(level, sweep, comm, size)
+            if sweep >= 2 and movers.numel() < max(nl // 1000, 1):
+                break
+        uniq, dense = torch.unique(comm, return_inverse=True)
+        if uniq.numel() == nl:                     # every community is one supernode: a refined sub-community, so connected
+            return dense[labels]
+        sub = refine(rowptr, col, w, k, size, comm, two_m, resolution, cap, max_sweeps, level, on_refine)
+        usub, dsub = torch.unique(sub, return_inverse=True)
+        labels = dsub[labels]
+        if usub.numel() == nl or level == max_levels - 1:
+            return labels                          # the refined partition: connected whichever way the loop ends
+        comm = torch.zeros(usub.numel(), dtype=torch.int32, device=dev)
+        comm[dsub] = dense.to(torch.int32)         # the communities carried onto the supernodes
+        rowptr, col, w = _aggregate(rowptr, col, w, dsub, usub.numel())
+        k = torch.zeros(usub.numel(), dtype=torch.int64, device=dev).index_add_(0, dsub, k)
+        size = torch.zeros(usub.numel(), dtype=torch.int64, device=dev).index_add_(0, dsub, size)
     return labels
 
 
@@ -265,13 +383,16 @@ def order_by_labels(labels, deg):
     return order[torch.argsort(dense[order], stable=True)], dense
 
 
-def cog_order(graph, batch_size, max_comm_size=None, **louvain_kw):
-    """CoG's preprocessing in one call: `louvain` communities (capped at max_comm_size), ordered largest first (hubs first inside),
-    merged into groups of >= batch_size nodes, relabelled contiguously.  Returns a CommunityBook."""
+def cog_order(graph, batch_size, max_comm_size=None, method="louvain", **kw):
+    """CoG's preprocessing in one call: `louvain` (the default) or `leiden` communities (capped at max_comm_size; **kw goes to the
+    method), ordered largest first (hubs first inside), merged into groups of >= batch_size nodes, relabelled contiguously.
+    Returns a CommunityBook."""
     graph = _square(graph)
+    if method not in ("louvain", "leiden"):
+        raise ValueError("cog_order method must be 'louvain' or 'leiden'")
     if int(batch_size) < 1:
         raise ValueError("batch_size must be >= 1")
-    labels = louvain(graph, max_comm_size=max_comm_size, **louvain_kw)
+    labels = (leiden if method == "leiden" else louvain)(graph, max_comm_size=max_comm_size, **kw)
     order, dense = order_by_labels(labels, graph.degrees())
     counts = torch.bincount(dense)
     cptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=order.device)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""CoG / CommGNN training: size-capped Louvain communities found on the device, merged into groups of at least a batch, the graph
+"""CoG / CommGNN training: size-capped Louvain (or, with --method leiden, Leiden) communities found on the device, merged into groups of at least a batch, the graph
 relabelled so that every group is a contiguous id range, and a 2-layer GCN trained on one group's induced subgraph at a time (the
 reference's cog.py + CommGNN_train.py; Cluster-GCN style batches):
 
     python examples/cog/train.py --nodes 200000 --epochs 5
     python examples/cog/train.py --nodes 20000 --batch 2000 --max-comm-size 1000 --epochs 4
+    python examples/cog/train.py --nodes 20000 --batch 2000 --method leiden      # every community connected
 """
 import argparse
 import os
@@ -37,6 +38,7 @@ def main():
     ap.add_argument("--classes", type=int, default=47)
     ap.add_argument("--batch", type=int, default=20_000)
     ap.add_argument("--max-comm-size", type=int, default=None, help="community size cap (default: the batch size)")
+    ap.add_argument("--method", choices=("louvain", "leiden"), default="louvain", help="leiden: refined, connected communities")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
@@ -50,12 +52,12 @@ def main():
     feats = torch.randn(n, args.feats, device=dev) + torch.nn.functional.one_hot(labels % args.feats, args.feats) * 2.0
     cap = args.batch if args.max_comm_size is None else args.max_comm_size
     t0 = time.time()
-    loader = CommunityBatchLoader(g, feats, labels, args.batch, shuffle=True, seed=args.seed, max_comm_size=cap)
+    loader = CommunityBatchLoader(g, feats, labels, args.batch, shuffle=True, seed=args.seed, max_comm_size=cap, method=args.method)
     torch.cuda.synchronize()
     book = loader.book
     sizes = book.community_ranges[:, 1] - book.community_ranges[:, 0]
-    print("cog: %d communities (largest %d, cap %d) in %d groups, modularity %.4f, %.2f s"
-          % (sizes.numel(), int(sizes.max()), cap, len(loader), community.modularity(loader.graph, book.community), time.time() - t0))
+    print("cog (%s): %d communities (largest %d, cap %d) in %d groups, modularity %.4f, %.2f s"
+          % (args.method, sizes.numel(), int(sizes.max()), cap, len(loader), community.modularity(loader.graph, book.community), time.time() - t0))
     train = torch.rand(n, device=dev) < 0.5                                       # in the book's id space, as the batches are
     model = Model(args.feats, 128, args.classes).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=3e-3)

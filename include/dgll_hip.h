@@ -776,6 +776,25 @@ int dgll_hip_louvain_move(void* stream, const int64_t* rowptr, const int32_t* co
                           uint32_t sweep, int all_active, int wave_max_deg, int block_max_deg, void* scratch, size_t scratch_bytes,
                           int32_t* target, int64_t* info);
 size_t dgll_hip_louvain_scratch_bytes(int64_t n, int64_t long_slots);
+/* Leiden's refinement, one synchronous sweep of one level (dgll_amd/community.py runs the sweeps and the levels).  The level's
+ * graph, k, size, two_m, cap, the tiers, `scratch` (same layout and size rule, over all rows longer than block_max_deg) and `info`
+ * as for dgll_hip_louvain_move.  bound int32 [n] in [0, n): the community local moving found, which a node never leaves here; totP
+ * int64 [n]: the sum of k per bound community; sub int32 [n] in [0, n): the sub-communities at the start of the sweep, tot / csize /
+ * cnt theirs.  Only the entries (v, u) with u != v and bound[u] == bound[v] count; W(v, S) is their weight into sub-community S.
+ * First pass, every row: wC[v] = sum over S of W(v, S), wS[v] = W(v, sub[v]), cut[S] = sum over the members of S of wC - wS (the
+ * weight between S and the rest of its bound community; integer atomics, zeroed here).  Second pass: node v of bound community p
+ * decides when cnt[sub[v]] == 1 and (double)wC[v] >= resolution * (double)k_v * (double)(totP_p - k_v) / (double)two_m; then
+ * target[v] = the sub-community S != sub[v] among v's neighbours in p with csize_S + size_v <= cap, not (cnt_S == 1 && S > sub[v]),
+ *     (double)cut_S >= resolution * (double)tot_S * (double)(totP_p - tot_S) / (double)two_m     and
+ *     gain(S) = (double)W(v, S) - resolution * (double)k_v * (double)tot_S / (double)two_m > 0
+ * that has the largest gain, ties to the smallest id; sub[v] for every other node.  Float64 left to right, no contraction.
+ * info[0] += nodes whose target differs from their sub-community; info[1] |= the error bits of dgll_hip_louvain_move (8: a
+ * sub-community id outside [0, n)) and 16: a bound id outside [0, n) (the node keeps its sub-community, its sums are 0).        */
+int dgll_hip_leiden_refine(void* stream, const int64_t* rowptr, const int32_t* col, const int64_t* w, const int64_t* k,
+                           const int64_t* size, const int32_t* sub, const int32_t* bound, const int64_t* tot, const int64_t* csize,
+                           const int32_t* cnt, const int64_t* totP, int64_t n, int64_t nnz, int64_t two_m, double resolution,
+                           int64_t cap, int wave_max_deg, int block_max_deg, void* scratch, size_t scratch_bytes, int32_t* target,
+                           int64_t* wS, int64_t* wC, int64_t* cut, int64_t* info);
 
 
 /* ---- a10: H = relu(A_csr . (X[:, :actual_F] . W[:actual_F, :])) --------------------------------------------
