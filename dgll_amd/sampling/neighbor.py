@@ -1,0 +1,139 @@
+"""Node-wise neighbour sampler with DGL's block contract, on the device (dgll_amd/csrc/neighbor.hip).
+
+The reference's two headline scripts (`GPU Accelerator/MQGCN.py:114`, `MQGraphSAGE.py:114`) build `NeighborSampler([4, 4])` and
+iterate `(input_nodes, output_nodes, blocks)`: fan-out sampling WITHOUT replacement, every hop compacted into a message-flow-graph
+block whose source nodes are unique, the destinations first.
+
+    NeighborSampler(fanouts, g=None, replace=False, norm="mean", device=None)
+
+fanouts: DGL's order -- fanouts[i] belongs to layer i, the last entry is applied to the seeds first; -1 keeps every neighbour; a
+fan-out is at most MAX_FANOUT (64: one kept position per lane of a wavefront).  replace=True is refused (out of scope).  g: a
+CSRGraph of IN-neighbours (row v lists the sources of v) or a DGraph, converted once; it may also be passed to the first sample().
+
+sample(g, seed_nodes) / sample_seeded(g, seed_nodes, seed) -> (input_nodes, output_nodes, blocks), blocks outermost first.  Each
+block is a CSRGraph with int64 rowptr, int32 LOCAL column ids ascending within a row, n_rows = |dst|, n_cols = |src|:
+blocks[i].n_rows == blocks[i + 1].n_cols, blocks[-1].n_rows == len(seed_nodes).  The source nodes of a block are [its destinations
+in their order | the new nodes in ascending id order], so `input_nodes[:blocks[0].n_rows]` are blocks[0]'s destinations and
+`x[:block.n_rows]` is a layer's self term.  norm="mean": fp32 values 1 / count per row (rows without neighbours have no entries);
+norm=None: no values.  A destination of degree d keeps min(d, fanout) DISTINCT entries of its adjacency list, every subset equally
+likely (Floyd's algorithm on Philox4x32-10 words; counter = (node, layer, call), key = seed: the draw of a node does not depend
+on its batch).  Seed nodes must be unique and lie in [0, N): both are checked on the device and raise.
+
+Differences from DGL: the new nodes of a block are in ascending id order (DGL: first occurrence); the generator differs, so the
+sampled ids are not DGL's.  Parallel edges of the graph are kept as they are (a block row may then repeat a column).
+
+Seeding, streams: as the layer-wise samplers (sampling/layerwise.py) -- sample() draws one 64-bit seed from numpy's global
+generator, sample_seeded takes it (use fast_sampler.batch_seed per batch; MiniBatchPipeline(sampler_threads=K) does); the kernels
+run on a stream the sampler owns, sample() returns after it has finished, and a consumer on another stream calls
+`layerwise.record_stream(blocks, input_nodes, stream)`.  One blocking device -> host read per layer (nnz and the number of new nodes).
+"""
+import threading
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..graph import CSRGraph
+from .layerwise import _as_device_csr, record_stream  # noqa: F401  (record_stream: re-exported for consumers)
+
+MAX_FANOUT = int(_lib.lib.dgll_hip_nb_max_fanout())
+_INFO_WORDS = 8              # neighbor.hip: {nnz, new nodes, error bits, ...}
+_ERRORS = {1: "a seed / destination id outside [0, N)", 2: "a column id of the graph outside [0, N)", 4: "a duplicate seed node"}
+
+
+class NeighborSampler:
+    def __init__(self, fanouts, g=None, replace=False, norm="mean", device=None):
+        if replace:
+            raise NotImplementedError("NeighborSampler samples without replacement only (replace=True is not supported)")
+        fanouts = [int(f) for f in np.asarray(fanouts).reshape(-1)]
+        if not fanouts or any(f != -1 and not 1 <= f <= MAX_FANOUT for f in fanouts):
+            raise ValueError("fanouts must be a non-empty list of -1 (every neighbour) or integers in [1, %d]" % MAX_FANOUT)
+        if norm not in ("mean", None):
+            raise ValueError("norm must be 'mean' or None")
+        self.fanouts, self.layers, self.norm = fanouts, len(fanouts), norm
+        self._device_arg = device
+        self.graph = None
+        self._lock = threading.Lock()
+        if g is not None:
+            self._bind(g)
+
+    def _bind(self, g):
+        device = self._device_arg
+        if device is None:
+            if isinstance(g, CSRGraph) and g.is_cuda:
+                device = g.device
+            elif not torch.cuda.is_available():
+                raise RuntimeError("NeighborSampler runs on the GPU and none is available: pass a graph on the device or device=")
+            else:
+                device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        self.graph = g = _as_device_csr(g, self.device)
+        self.num_nodes = n = g.n_rows
+        if not 0 < n < 2 ** 31:
+            raise ValueError("the graph needs between 1 and 2^31 - 1 nodes")
+        words = (n + 31) // 32
+        z = lambda k: torch.zeros(k, dtype=torch.int32, device=self.device)      # noqa: E731
+        # persistent per graph: epoch tags (never cleared) and the destinations' local ids; per layer: the bitmap of new nodes
+        self._mark, self._local, self._bitmap, self._prefix = z(n), z(n), z(words), z(words)
+        self._epoch = 0
+        self.stream = torch.cuda.Stream(self.device)
+
+    def sample(self, g, seed_nodes):
+        """(input_nodes, output_nodes, blocks) under a seed drawn from numpy's global generator."""
+        seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64))
+        return self.sample_seeded(g, seed_nodes, seed)
+
+    def _seed_tensor(self, seed_nodes):
+        if isinstance(seed_nodes, torch.Tensor):
+            b = seed_nodes.to(torch.int64)
+        else:
+            b = torch.as_tensor(np.asarray(seed_nodes, dtype=np.int64))
+        return b.reshape(-1).to(self.device, non_blocking=False).contiguous()
+
+    def _layer(self, rows, fanout, seed, layer, st):
+        """One hop: (source nodes, block) of the destinations `rows`."""
+        g, dev, n_dst = self.graph, self.device, int(rows.numel())
+        rowptr = torch.zeros(n_dst + 1, dtype=torch.int64, device=dev)
+        want_val = self.norm == "mean"
+        if n_dst == 0:
+            col = torch.empty(0, dtype=torch.int32, device=dev)
+            val = torch.empty(0, dtype=torch.float32, device=dev) if want_val else None
+            return rows, CSRGraph(rowptr, col, val, 0, 0, check=False)
+        info = torch.empty(_INFO_WORDS, dtype=torch.int64, device=dev)
+        cap = n_dst * fanout if fanout > 0 else 0
+        drawn = torch.empty(cap, dtype=torch.int32, device=dev) if cap else None
+        self._epoch = epoch = self._epoch % 0xFFFFFFFF + 1
+        _lib.launch("dgll_hip_nb_sample", dev, g.rowptr.data_ptr(), g.col.data_ptr(), self.num_nodes, rows.data_ptr(), n_dst, fanout,
+                    int(seed) & 0xFFFFFFFFFFFFFFFF, layer, self._mark.data_ptr(), self._local.data_ptr(), epoch, self._bitmap.data_ptr(),
+                    self._prefix.data_ptr(), _lib.ptr(drawn), cap, rowptr.data_ptr(), info.data_ptr(), stream=st)
+        nnz, n_new, err = info.cpu().tolist()[:3]           # the one blocking read of the layer
+        if err:
+            raise ValueError("neighbour sampler: " + ", ".join(m for bit, m in _ERRORS.items() if err & bit))
+        src = torch.empty(n_dst + n_new, dtype=torch.int64, device=dev)
+        col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        loc = torch.empty(nnz, dtype=torch.int32, device=dev)
+        val = torch.empty(nnz, dtype=torch.float32, device=dev) if want_val else None
+        _lib.launch("dgll_hip_nb_block", dev, g.rowptr.data_ptr(), g.col.data_ptr(), self.num_nodes, rows.data_ptr(), n_dst, fanout,
+                    self._mark.data_ptr(), self._local.data_ptr(), epoch, self._bitmap.data_ptr(), self._prefix.data_ptr(), _lib.ptr(drawn),
+                    rowptr.data_ptr(), nnz, n_new, _lib.ptr(loc) if nnz else None, src.data_ptr(), _lib.ptr(col) if nnz else None,
+                    _lib.ptr(val) if nnz else None, stream=st)
+        return src, CSRGraph(rowptr, col, val, n_dst, n_dst + n_new, check=False)
+
+    def sample_seeded(self, g, seed_nodes, seed, max_threads=1, last_hop_buffer=None, staging=None):
+        """sample() under an explicit 64-bit seed: bit-identical output for the same (graph, seed nodes, seed).  max_threads,
+        last_hop_buffer and staging are the host sampler's options (MiniBatchPipeline passes them to every sampler): unused here."""
+        with self._lock:
+            if self.graph is None:
+                if g is None:
+                    raise ValueError("NeighborSampler needs a graph: pass it to the constructor or to sample()")
+                self._bind(g)
+            with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+                st = self.stream
+                rows = self._seed_tensor(seed_nodes)
+                blocks = []
+                for layer in range(self.layers - 1, -1, -1):
+                    rows, blk = self._layer(rows, self.fanouts[layer], seed, layer, st)
+                    blocks.append(blk)
+                st.synchronize()
+        blocks.reverse()
+        return rows, seed_nodes, blocks

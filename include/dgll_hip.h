@@ -681,6 +681,33 @@ int dgll_hip_lw_block_fill(void* stream, const int64_t* rowptr, const int32_t* c
 int dgll_host_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
 
 
+/* ---- neighbour sampling into message-flow-graph blocks (dgll_amd/sampling/neighbor.py) --------------------------------------
+ * The graph is a CSR of in-neighbours (int64 rowptr, int32 col) over n_total < 2^31 nodes, every row shorter than 2^32; rows
+ * (int64[n_rows], distinct) are the destinations of one layer.  Destination row r with id v and degree d keeps all d entries when
+ * fanout == -1 or d <= fanout, otherwise `fanout` distinct positions of v's adjacency list, every subset equally likely, by
+ * Floyd's algorithm: for i = 0 .. fanout-1, j = d - fanout + i, t = mulhi32(word_i, j + 1), take t unless taken, else j; word_i is
+ * word i % 4 of Philox4x32-10 with key = {seed lo, seed hi} and counter = {v lo, v hi, layer, i / 4}.  The draw of (seed, layer, v,
+ * fanout) depends on nothing else.  Kept entries stay in ascending position.
+ * Workspaces that persist per graph: mark uint32[n_total] (epoch tags: start zeroed, never cleared, every call passes a fresh
+ * non-zero epoch), local int32[n_total]; per call: bitmap uint32[ceil(n_total / 32)] (cleared here), prefix int32[the same],
+ * drawn int32[drawn_cap >= n_rows * fanout] (unused and may be NULL when fanout == -1: the entries are the graph's own).
+ * Outputs: out_rowptr int64[n_rows + 1]; info int64[8] (zeroed here) = {nnz, number of drawn nodes that are no destination, error
+ * bits: 1 a row id outside [0, n_total), 2 a column id outside it, 4 a destination listed twice}.  The caller reads info once,
+ * sizes the outputs and calls dgll_hip_nb_block with the same workspaces and epoch.                                              */
+int dgll_hip_nb_sample(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_total, const int64_t* rows, int64_t n_rows,
+                       int fanout, uint64_t seed, int layer, uint32_t* mark, int32_t* local, uint32_t epoch, uint32_t* bitmap,
+                       int32_t* prefix, int32_t* drawn, int64_t drawn_cap, int64_t* out_rowptr, int64_t* info);
+/* The block of that draw: src_nodes int64[n_rows + n_new] = [rows in their order | the new ids ascending]; out_col int32[nnz] local
+ * ids into src_nodes, ascending within a row; out_val fp32[nnz] = 1 / (entries of the row), or NULL for none.  loc: int32[nnz]
+ * workspace.  Only after info[2] == 0.                                                                                          */
+int dgll_hip_nb_block(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_total, const int64_t* rows, int64_t n_rows,
+                      int fanout, const uint32_t* mark, const int32_t* local, uint32_t epoch, const uint32_t* bitmap,
+                      const int32_t* prefix, const int32_t* drawn, const int64_t* out_rowptr, int64_t nnz, int64_t n_new,
+                      int32_t* loc, int64_t* src_nodes, int32_t* out_col, float* out_val);
+/* The largest fan-out dgll_hip_nb_sample draws (64: one kept position per lane of a wavefront).                                  */
+int dgll_hip_nb_max_fanout(void);
+
+
 /* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
  * Every random word is Philox4x32-10 with key = {seed lo, seed hi}.
  * Walks: CSR (int64 rowptr, int32 col, rows ascending when p or q != 1; dgll_hip_random_walk ignores edge values)
