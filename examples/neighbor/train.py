@@ -5,6 +5,7 @@ the GPU, each block's sources are unique with the destinations first, so a layer
     h_dst = W_self h[:n_dst] + W_neigh mean_{u in N(v)} h_u        (the mean is ops.spmm on the block's 1 / count values)
 
     python examples/neighbor/train.py --nodes 200000 --fanouts 10,25 --batch 1024 --epochs 3
+    python examples/neighbor/train.py --weighted       # edge-weighted sampling: NeighborSampler(prob=...), weight 1 / in-degree of the source
 """
 import argparse
 import os
@@ -51,6 +52,8 @@ def main():
     ap.add_argument("--fanouts", default="10,25", help="DGL's order: the last entry is applied to the seeds first; -1 = every neighbour")
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--weighted", action="store_true",
+                    help="sample neighbours in proportion to an edge weight (1 / in-degree of the source: hubs are drawn less often)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("this example runs the HIP kernels: a GPU is required")
@@ -63,7 +66,10 @@ def main():
     feats = torch.randn(n, args.feats) + torch.nn.functional.one_hot(labels % args.feats, args.feats) * 2.0
     dg = DGraph.from_csr(g.rowptr.cpu().numpy(), g.col.cpu().numpy().astype(np.int64), labels=labels, features=feats)
     fanouts = [int(f) for f in args.fanouts.split(",")]
-    sampler = NeighborSampler(fanouts, g)
+    prob = None
+    if args.weighted:                            # one weight per entry of g, in entry order; a source without in-neighbours counts as degree 1
+        prob = 1.0 / g.degrees().clamp(min=1).to(torch.float32)[g.col.long()]
+    sampler = NeighborSampler(fanouts, g, prob=prob)
     cache = GraphCacheServer(feats, gpuid=0)
     cache.auto_cache(g.degrees().cpu(), capacity=n // 2)
     model = SageMean(args.feats, 128, args.classes, layers=len(fanouts)).to(dev)

@@ -706,6 +706,20 @@ int dgll_hip_nb_block(void* stream, const int64_t* rowptr, const int32_t* col, i
                       int32_t* loc, int64_t* src_nodes, int32_t* out_col, float* out_val);
 /* The largest fan-out dgll_hip_nb_sample draws (64: one kept position per lane of a wavefront).                                  */
 int dgll_hip_nb_max_fanout(void);
+/* dgll_hip_nb_sample with an edge-weighted draw: weight fp32[nnz], one positive finite weight per entry of the graph (entries of
+ * weight 0 are removed by the caller beforehand).  fanout in [1, 64] only.  A row of degree d <= fanout is copied; otherwise
+ * position p of node v's row gets key = -log(u) / (double)weight in fp64, u = (bits + 0.5) * 2^-53, bits = ((x0 << 32) | x1) >> 11 of
+ * ONE Philox4x32-10 call with key = {seed lo, seed hi} and counter = {v lo, v hi, layer | 0x80000000, p}, and the `fanout` smallest
+ * by (key bits as uint64, position) are kept: successive draws without replacement in proportion to the weights.  Same outputs,
+ * workspaces and info as dgll_hip_nb_sample, then dgll_hip_nb_block with the same fanout; drawn: int32[drawn_cap],
+ * drawn_cap >= n_rows * (fanout + 1) (the last n_rows entries list the rows longer than dgll_hip_nb_long_row()).  info[2] bit 8: a
+ * weight that is no positive finite number was met (it is never selected).                                                      */
+int dgll_hip_nb_sample_weighted(void* stream, const int64_t* rowptr, const int32_t* col, const float* weight, int64_t n_total,
+                                const int64_t* rows, int64_t n_rows, int fanout, uint64_t seed, int layer, uint32_t* mark, int32_t* local,
+                                uint32_t epoch, uint32_t* bitmap, int32_t* prefix, int32_t* drawn, int64_t drawn_cap, int64_t* out_rowptr,
+                                int64_t* info);
+/* Rows of more entries than this are drawn by a workgroup each, shorter ones by a lane group (dgll_hip_nb_sample_weighted).      */
+int dgll_hip_nb_long_row(void);
 
 
 /* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
