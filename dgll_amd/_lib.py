@@ -53,6 +53,13 @@ class GatChoice(C.Structure):
                [("row_blocks", C.c_int64), ("chunk_blocks", C.c_int64), ("message", C.c_char_p)]
 
 
+class TransformChoice(C.Structure):
+    """include/dgll_hip.h: struct dgll_transform_choice (dgll_hip_debug_transform_choice)."""
+    _fields_ = [(n, C.c_int) for n in ("kernel", "nt", "ntw", "nc", "cs", "colsplit", "epi", "dual", "rows_per_block", "lds_bytes",
+                                       "per_cu", "bits_in_epilogue", "error")] + \
+               [("workgroups", C.c_int64), ("row_sequences", C.c_int64), ("n_blocks", C.c_int64), ("message", C.c_char_p)]
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -81,6 +88,7 @@ SIGNATURES = {
     "dgll_hip_debug_tune": (_i32, [_i32, _i32]),
     "dgll_hip_debug_spmm_choice": (_i32, [_i32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "dgll_hip_debug_gat_choice": (_i32, [_i32] * 17 + [_i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
+    "dgll_hip_debug_transform_choice": (_i32, [_i32] * 12 + [_i64, _i32, _vp]),
     "dgll_hip_csr_plan_create": (_i32, [_vp, _vp, _i64, _i64, _i32, C.POINTER(_vp)]),
     "dgll_hip_csr_plan_destroy": (None, [_vp]),
     "dgll_hip_csr_plan_workspace_bytes": (_sz, [_vp, _i32]),

@@ -8,8 +8,11 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "transform_choice.hpp"
 
 int g_tune_res_per_cu = 0;    // dgll_hip_debug_tune(11, v): workgroups per CU of the resident-weights transform (0 = default)
+int g_tune_res_grid_cap = 0;  // dgll_hip_debug_tune(16, v): cap on that kernel's grid, min(default, max(16, v / 16 * 16)) workgroups, so that
+                              // a persistent workgroup wraps to further row blocks at test sizes (0 = no cap, the shipped default)
 
 namespace dgll {
 
@@ -150,8 +153,8 @@ struct MfmaGemmArgs {
 #endif
 };
 
-constexpr int kChunkK = 64;                 // k per LDS stage
-constexpr int kWPitch = kChunkK * 2 + 16;   // bytes per weight row in LDS (144: bank-conflict-free b128 reads)
+constexpr int kChunkK = kTransformChunkK;   // k per LDS stage
+constexpr int kWPitch = kTransformWPitch;   // bytes per weight row in LDS (144: bank-conflict-free b128 reads)
 
 __device__ __forceinline__ uint4 mask_tail(uint4 v, int valid) {  // keep the first `valid` (0..8) bf16 of a vector
     uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -390,14 +393,14 @@ __global__ __launch_bounds__(kBlock, 2) void gemm_bf16_nt_kernel(const MfmaGemmA
 }
 
 template <int NT>
-static hipError_t launch_mfma(const MfmaGemmArgs& a, hipStream_t s) {
-    const size_t lds = 2 * (size_t)NT * 32 * kWPitch;
+static hipError_t launch_mfma(const MfmaGemmArgs& a, const TransformChoice& c, hipStream_t s) {
+    const size_t lds = (size_t)c.lds_bytes;
     if (lds > 48 * 1024) {
         static hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_kernel<NT>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // once: keeps
         if (raised != hipSuccess) return raised;                            // launches free of non-stream calls (graph capture)
     }
-    dim3 grid((uint32_t)((a.M + 127) / 128));
+    dim3 grid((uint32_t)c.workgroups);
     hipLaunchKernelGGL((gemm_bf16_nt_kernel<NT>), grid, dim3(kBlock), lds, s, a);
     return hipGetLastError();
 }
@@ -993,28 +996,29 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_res_kernel(const MfmaGemmAr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the loads issued past the last block (zero-byte descriptors)
 }
 
-template <int NTW, int NC, int CS, int COLSPLIT, int EPI, bool DUAL = false>
-static hipError_t launch_mfma_res_p(const MfmaGemmArgs& a, hipStream_t s);
-
-// which epilogue: 1 (plain) loads nothing; 2 = plain + the output gate as bits (fetched a phase ahead); 0 = everything else
-static int res_epilogue_kind(const MfmaGemmArgs& a) {
-    const bool simple = !a.out_f32 && !a.row_scale && !a.addend;
-    if (simple && !a.out_gate && !a.gate_bits) return 1;
-    if (simple && a.gate_bits && (a.ldo & 7) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15u) == 0) return 2;
-    return 0;
-}
-
-template <int NTW, int NC, int CS, int COLSPLIT>
-static hipError_t launch_mfma_res(const MfmaGemmArgs& a, hipStream_t s) {
-    switch (res_epilogue_kind(a)) {
-        case 1: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 1>(a, s);
-        case 2: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 2>(a, s);
-        default: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 0>(a, s);
+// the device's compute-unit count, cached per device id (single-process multi-device use)
+static hipError_t device_cu_count(int* n_cu) {
+    static int n_cu_of[64] = {};
+    *n_cu = 256;
+    int dev = 0;
+    hipError_t ge = hipGetDevice(&dev);
+    if (ge != hipSuccess) return ge;
+    const int slot = (dev >= 0 && dev < 64) ? dev : 0;
+    if (n_cu_of[slot] == 0 || slot != dev) {
+        hipDeviceProp_t prop;
+        int n = 0;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+        if (n <= 0) n = 256;
+        if (slot != dev) { *n_cu = n; return hipSuccess; }
+        n_cu_of[slot] = n;
     }
+    *n_cu = n_cu_of[slot];
+    return hipSuccess;
 }
 
-template <int NTW, int NC, int CS, int COLSPLIT, int EPI, bool DUAL>
-static hipError_t launch_mfma_res_p(const MfmaGemmArgs& a, hipStream_t s) {
+// one instantiation, in the geometry transform_choose() gave it (c.lds_bytes, c.workgroups)
+template <int NTW, int NC, int CS, int COLSPLIT, int EPI, bool DUAL = false>
+static hipError_t launch_mfma_res_p(const MfmaGemmArgs& a, const TransformChoice& c, hipStream_t s) {
     // ring depth: D | NC or NC | D (slot arithmetic)
 #ifdef DGLL_RES_D
     constexpr int D = (NC % DGLL_RES_D == 0 || DGLL_RES_D % NC == 0) ? DGLL_RES_D : NC;    // probe builds: forced ring depth
@@ -1022,22 +1026,11 @@ static hipError_t launch_mfma_res_p(const MfmaGemmArgs& a, hipStream_t s) {
     constexpr int D = 1;      // measured (tools/probes/res_trace.hip): more chunks in flight only queue -- see the header above; round 3,
                               // narrow outputs with the whole reduction of a row block in flight (D = NC): 256 -> 47 0.317 -> 0.34 ms
 #endif
-#ifdef DGLL_RES_RG
-    constexpr int RG = DGLL_RES_RG;
-#else
-    constexpr int RG = 2;
-#endif
-#ifdef DGLL_RES_NW
-    constexpr int NW = DGLL_RES_NW;
-#else
-    constexpr int NW = 8;
-#endif
-    constexpr int NWG_T = NTW * CS;
-    const size_t lds = (size_t)NC * NWG_T * 32 * 128 + NW * 32 * 80 + NWG_T * 32 * 4;
+    constexpr int RG = kResRG, NW = kResNW;
+    const size_t lds = (size_t)c.lds_bytes;
     auto kern = &gemm_bf16_res_kernel<NTW, RG, NC, CS, COLSPLIT, D, EPI, NW, DUAL>;
-    // both the LDS attribute and the CU count are per device (single-process multi-device use): cached per device id
+    // the LDS attribute is per device (single-process multi-device use): cached per device id
     static bool raised_on[64] = {};
-    static int n_cu_of[64] = {};
     int dev = 0;
     hipError_t ge = hipGetDevice(&dev);
     if (ge != hipSuccess) return ge;
@@ -1047,57 +1040,82 @@ static hipError_t launch_mfma_res_p(const MfmaGemmArgs& a, hipStream_t s) {
         if (re != hipSuccess) return re;
         raised_on[slot] = slot == dev;
     }
-    if (n_cu_of[slot] == 0 || slot != dev) {
-        hipDeviceProp_t prop;
-        int n = 0;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-        n = n / 16 * 16;                                    // whole groups of 8 XCDs x COLSPLIT partners
-        if (n <= 0) n = 16;
-        n_cu_of[slot] = n;
-    }
-    const int n_cu = n_cu_of[slot];
-    int per_cu = lds > 80 * 1024 ? 1 : 2;
-    if (g_tune_res_per_cu > 0 && (size_t)g_tune_res_per_cu * lds <= 160 * 1024) per_cu = g_tune_res_per_cu;   // diagnostics
-    dim3 grid((uint32_t)(n_cu * per_cu));
+    dim3 grid((uint32_t)c.workgroups);
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
     return hipGetLastError();
 }
 
-// resident-weights kernel for this shape?  nt = 32-column tiles of N, n_chunks = 64-k chunks of K1 + K2
-static bool res_applies(int nt, int n_chunks) {
-    if (n_chunks < 1 || n_chunks > 8) return false;
-    if (nt > 4 && n_chunks > 4) return nt <= 8;            // 256 columns x 512 k: two workgroups of 128 columns
-    return (size_t)n_chunks * (nt <= 2 ? 2 : nt <= 4 ? 4 : 8) * 32 * 128 <= 128 * 1024;
+template <int NTW, int NC, int CS, int COLSPLIT>
+static hipError_t launch_mfma_res(const MfmaGemmArgs& a, const TransformChoice& c, hipStream_t s) {
+    switch (c.epi) {
+        case 1: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 1>(a, c, s);
+        case 2: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 2>(a, c, s);
+        default: return launch_mfma_res_p<NTW, NC, CS, COLSPLIT, 0>(a, c, s);
+    }
 }
 
-static hipError_t launch_mfma_res_dispatch(const MfmaGemmArgs& a, int nt, int n_chunks, hipStream_t s) {
+// the resident instantiation transform_choose() named: (ntw, cs, colsplit) is one of four families, nc = 1 .. 8
+static hipError_t launch_mfma_res_dispatch(const MfmaGemmArgs& a, const TransformChoice& c, hipStream_t s) {
 #ifdef DGLL_RES_PROBE          // probe builds instantiate the few kernels they launch themselves (3 minutes of compile time otherwise)
-    (void)a; (void)nt; (void)n_chunks; (void)s;
+    (void)a; (void)c; (void)s;
     return hipErrorNotSupported;
 #else
-#define RES_NC(NTW, CS, COLSPLIT)                                                      \
-    switch (n_chunks) {                                                                \
-        case 1: return launch_mfma_res<NTW, 1, CS, COLSPLIT>(a, s);                    \
-        case 2: return launch_mfma_res<NTW, 2, CS, COLSPLIT>(a, s);                    \
-        case 3: return launch_mfma_res<NTW, 3, CS, COLSPLIT>(a, s);                    \
-        case 4: return launch_mfma_res<NTW, 4, CS, COLSPLIT>(a, s);                    \
-        case 5: return launch_mfma_res<NTW, 5, CS, COLSPLIT>(a, s);                    \
-        case 6: return launch_mfma_res<NTW, 6, CS, COLSPLIT>(a, s);                    \
-        case 7: return launch_mfma_res<NTW, 7, CS, COLSPLIT>(a, s);                    \
-        default: return launch_mfma_res<NTW, 8, CS, COLSPLIT>(a, s);                   \
+#define RES_NC(NTW, CS, COLSPLIT)                                                         \
+    switch (c.nc) {                                                                       \
+        case 1: return launch_mfma_res<NTW, 1, CS, COLSPLIT>(a, c, s);                    \
+        case 2: return launch_mfma_res<NTW, 2, CS, COLSPLIT>(a, c, s);                    \
+        case 3: return launch_mfma_res<NTW, 3, CS, COLSPLIT>(a, c, s);                    \
+        case 4: return launch_mfma_res<NTW, 4, CS, COLSPLIT>(a, c, s);                    \
+        case 5: return launch_mfma_res<NTW, 5, CS, COLSPLIT>(a, c, s);                    \
+        case 6: return launch_mfma_res<NTW, 6, CS, COLSPLIT>(a, c, s);                    \
+        case 7: return launch_mfma_res<NTW, 7, CS, COLSPLIT>(a, c, s);                    \
+        default: return launch_mfma_res<NTW, 8, CS, COLSPLIT>(a, c, s);                   \
     }
-    if (nt <= 2) { RES_NC(2, 1, 1) }                        // N <= 64: one wave per row group, all columns
-    if (nt <= 4) { RES_NC(4, 1, 1) }                        // N <= 128
-    if (n_chunks <= 4) { RES_NC(4, 2, 1) }                  // N <= 256, K <= 256: two waves per row group
+    if (c.ntw == 2) { RES_NC(2, 1, 1) }                     // N <= 64: one wave per row group, all columns
+    if (c.cs == 1 && c.colsplit == 1) { RES_NC(4, 1, 1) }   // N <= 128
+    if (c.cs == 2) { RES_NC(4, 2, 1) }                      // N <= 256, K <= 256: two waves per row group
     RES_NC(4, 1, 2)                                         // N <= 256, K <= 512: two workgroups per row block
 #undef RES_NC
 #endif
 }
 
+#ifdef DGLL_RES_PROBE
+// probe builds (tools/probes/*.hip) launch one instantiation of their own choosing: the epilogue kind and the grid still come from
+// the choice header's helpers
+template <int NTW, int NC, int CS, int COLSPLIT>
+static hipError_t launch_mfma_res(const MfmaGemmArgs& a, hipStream_t s) {
+    TransformDesc d{};
+    d.out_f32 = a.out_f32 != 0; d.row_scale = a.row_scale != nullptr; d.addend = a.addend != nullptr; d.out_gate = a.out_gate != nullptr;
+    d.gate_bits = a.gate_bits != nullptr; d.out_aligned = (a.ldo & 7) == 0 && aligned16(a.out);
+    TransformChoice c{};
+    c.epi = res_epilogue_kind(d);
+    const size_t lds = res_lds_bytes(NTW, NC, CS);
+    c.lds_bytes = (int)lds;
+    int n_cu = 256;
+    hipError_t ge = device_cu_count(&n_cu);
+    if (ge != hipSuccess) return ge;
+    c.workgroups = res_grid(lds, n_cu, TransformTune{0, g_tune_res_per_cu, g_tune_res_grid_cap}, &c.per_cu);
+    return launch_mfma_res<NTW, NC, CS, COLSPLIT>(a, c, s);
+}
+#endif
+
 }  // namespace dgll
 
 int g_tune_mfma_kperm = 0;   // dgll_hip_debug_tune(4, v): 0 = per-shape choice (shipped), 1 = 4-wave kernel always, 2 = no chunk rotation
+
+static dgll::TransformTune transform_tune() { return dgll::TransformTune{g_tune_mfma_kperm, g_tune_res_per_cu, g_tune_res_grid_cap}; }
+
+DGLL_API int dgll_hip_debug_transform_choice(int N, int K1, int K2, int mask, int out_f32, int row_scale, int addend, int out_gate,
+                                             int gate_bits, int out_aligned, int ldw_equal, int dual, int64_t M, int n_cu,
+                                             dgll_transform_choice* out) {
+    DGLL_REQUIRE(out != nullptr, "out is NULL");
+    DGLL_REQUIRE(N > 0 && K1 > 0 && K2 >= 0 && M > 0, "bad launch description");
+    *out = dgll::transform_choose(dgll::TransformDesc{N, K1, dual ? 0 : K2, mask != 0, out_f32 != 0, row_scale != 0, addend != 0,
+                                                      out_gate != 0, gate_bits != 0, out_aligned != 0, K2 == 0 || ldw_equal != 0,
+                                                      dual != 0, M, n_cu}, transform_tune());
+    if (out->error != DGLL_OK) dgll::set_error(out->message);
+    return out->error;
+}
 
 // ---- weight packing: [n, k] fp32 / bf16 with arbitrary element strides (a parameter or its transposed view) -> the zero-padded
 // bf16 [rows, ld] block the transform kernels stage.  ONE launch where the wrappers used to cast, zero-fill and copy (three).
@@ -1200,7 +1218,12 @@ DGLL_API int dgll_hip_transform_bf16_dual(void* stream, const void* A, int64_t l
     DGLL_REQUIRE(M >= 0 && N >= 0 && K >= 0, "negative size");
     if (M == 0 || N == 0) return DGLL_OK;
     DGLL_REQUIRE(A && Wt1 && Wt2 && out1 && out2 && K > 0, "NULL operand");
-    DGLL_REQUIRE(N <= 256 && K <= 256, "dgll_hip_transform_bf16_dual: N, K <= 256 (both weight matrices stay resident in LDS)");
+    int n_cu = 0;
+    const hipError_t cu_err = device_cu_count(&n_cu);
+    TransformDesc d{};
+    d.N = N; d.K1 = K; d.ldw_equal = true; d.dual = true; d.M = M; d.n_cu = n_cu;
+    const TransformChoice c = transform_choose(d, transform_tune());
+    if (c.error != DGLL_OK) { set_error(c.message); return c.error; }
     DGLL_REQUIRE(wt_rows >= 256, "Wt1 / Wt2 must be zero-padded to 256 rows");
     DGLL_REQUIRE(aligned16(A) && (lda * 2) % 16 == 0 && lda >= ((K + 7) / 8) * 8, "A: 16-byte aligned rows");
     DGLL_REQUIRE(aligned16(Wt1) && aligned16(Wt2) && (ldw * 2) % 16 == 0 && ldw >= ((K + 63) / 64) * 64,
@@ -1213,13 +1236,15 @@ DGLL_API int dgll_hip_transform_bf16_dual(void* stream, const void* A, int64_t l
     a.pairs = 1;
     a.out = out1; a.ldo = ldo1; a.out2 = out2; a.ldo2 = ldo2; a.M = M; a.N = N;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipErrorNotSupported;
+    hipError_t e = cu_err != hipSuccess ? cu_err : hipErrorNotSupported;
 #ifndef DGLL_RES_PROBE
-    switch ((K + kChunkK - 1) / kChunkK) {             // 256 columns per workgroup (two waves per row group), two workgroups per row block
-        case 1: e = launch_mfma_res_p<4, 1, 2, 2, 1, true>(a, s); break;
-        case 2: e = launch_mfma_res_p<4, 2, 2, 2, 1, true>(a, s); break;
-        case 3: e = launch_mfma_res_p<4, 3, 2, 2, 1, true>(a, s); break;
-        default: e = launch_mfma_res_p<4, 4, 2, 2, 1, true>(a, s); break;
+    if (cu_err == hipSuccess) {
+        switch (c.nc) {                                // 256 columns per workgroup (two waves per row group), two workgroups per row block
+            case 1: e = launch_mfma_res_p<4, 1, 2, 2, 1, true>(a, c, s); break;
+            case 2: e = launch_mfma_res_p<4, 2, 2, 2, 1, true>(a, c, s); break;
+            case 3: e = launch_mfma_res_p<4, 3, 2, 2, 1, true>(a, c, s); break;
+            default: e = launch_mfma_res_p<4, 4, 2, 2, 1, true>(a, c, s); break;
+        }
     }
 #endif
     if (e != hipSuccess) return hip_fail(e, "gemm_bf16_res_kernel (dual) launch");
@@ -1235,7 +1260,16 @@ static int transform_bf16_impl(void* stream, const void* A1, int64_t lda1, int K
     DGLL_REQUIRE(M >= 0 && N >= 0 && K1 >= 0 && K2 >= 0, "negative size");
     if (M == 0 || N == 0) return DGLL_OK;
     DGLL_REQUIRE(A1 && Wt1 && out && K1 > 0, "NULL operand");
-    DGLL_REQUIRE(N <= 256, "dgll_hip_transform_bf16 keeps all N <= 256 output columns of a row block in accumulators");
+    // Which kernel, in which geometry: transform_choose() (transform_choice.hpp) from plain values -- the refusals that depend on
+    // them alone are its own (N > 256 here, gate bits nobody can read below)
+    int n_cu = 0;
+    const hipError_t cu_err = device_cu_count(&n_cu);     // (reported only if the kernel that needs the count is chosen)
+    TransformDesc d{};
+    d.N = N; d.K1 = K1; d.K2 = A2 ? K2 : 0; d.mask = relu_mask != nullptr; d.out_f32 = out_dtype == DGLL_F32;
+    d.row_scale = row_scale != nullptr; d.addend = addend != nullptr; d.out_gate = out_gate != nullptr; d.gate_bits = gate_bits != nullptr;
+    d.out_aligned = (ldo & 7) == 0 && aligned16(out); d.ldw_equal = !A2 || ldw1 == ldw2; d.M = M; d.n_cu = n_cu;
+    const TransformChoice c = transform_choose(d, transform_tune());
+    if (c.error != DGLL_OK && N > 256) { set_error(c.message); return c.error; }
     DGLL_REQUIRE(wt_rows >= (N <= 64 ? 64 : N <= 128 ? 128 : 256),
                  "Wt must be zero-padded to 64 / 128 / 256 rows (the kernel stages whole 32-row tiles of it)");
     DGLL_REQUIRE(out_dtype == DGLL_F32 || out_dtype == DGLL_BF16, "out_dtype");
@@ -1271,28 +1305,19 @@ static int transform_bf16_impl(void* stream, const void* A1, int64_t lda1, int K
                  "bits_out: uint32 [M, ld >= 4 * ceil(N / 128)], ld a multiple of 4, 16-byte aligned; bf16 output only");
     a.gate_bits = gate_bits; a.ld_gate_bits = ld_gate_bits; a.bits_out = bits_out; a.ld_bits_out = ld_bits_out;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nt = (N + 31) / 32;
     hipError_t e;
-    const int n_chunks = (K1 + kChunkK - 1) / kChunkK + (A2 ? (K2 + kChunkK - 1) / kChunkK : 0);
     a.no_rotate = g_tune_mfma_kperm == 2;
-    // Which kernel (tools/transform_probe.py, M = 2.45 M): the persistent resident-weights kernel wherever the weights of the
-    // whole reduction fit LDS (K1 + K2 <= 512) -- fused 256+256 -> 256: 0.90 ms against 1.2-1.4 for the 4-wave kernel, single
-    // 256 -> 256: 0.59 against 0.82, 256 -> 47: 0.37 against 0.40.  The 4-wave kernel keeps the input-mask form and longer
-    // reductions (weights staged per chunk).
-    const bool res = g_tune_mfma_kperm != 1 && !a.mask && res_applies(nt, n_chunks) && a.ldw[0] == (a.pairs > 1 ? a.ldw[1] : a.ldw[0]);
-    // the bits are an ALTERNATIVE reading of the gate: only the resident-weights kernel's bit epilogue takes them; every other path
-    // reads out_gate, which must then be there too
-    DGLL_REQUIRE(!gate_bits || out_gate || (res && res_epilogue_kind(a) == 2),
-                 "gate_bits alone: this shape / operand set runs a kernel that reads the gate as bf16 -- pass out_gate as well");
-    const bool epilogue_bits = res && res_epilogue_kind(a) != 0;      // the plain / bit-gated epilogues write the sign bits themselves
+    if (c.error != DGLL_OK) { set_error(c.message); return c.error; }
+    const bool epilogue_bits = c.bits_in_epilogue != 0;   // the plain / bit-gated epilogues write the sign bits themselves
     if (!epilogue_bits) a.bits_out = nullptr;
-    if (res) {
-        e = launch_mfma_res_dispatch(a, nt, n_chunks, s);
+    if (c.kernel == 1) {
+        if (cu_err != hipSuccess) return hip_fail(cu_err, "gemm_bf16_res_kernel launch");
+        e = launch_mfma_res_dispatch(a, c, s);
         if (e != hipSuccess) return hip_fail(e, "gemm_bf16_res_kernel launch");
     } else {
-        if (nt <= 2) e = launch_mfma<2>(a, s);
-        else if (nt <= 4) e = launch_mfma<4>(a, s);
-        else e = launch_mfma<8>(a, s);
+        if (c.nt == 2) e = launch_mfma<2>(a, c, s);
+        else if (c.nt == 4) e = launch_mfma<4>(a, c, s);
+        else e = launch_mfma<8>(a, c, s);
         if (e != hipSuccess) return hip_fail(e, "gemm_bf16_nt_kernel launch");
     }
     if (bits_out && !epilogue_bits) {                    // the general epilogue and the 4-wave kernel: one pass over what they wrote

@@ -916,6 +916,7 @@ DGLL_API int dgll_hip_csr_plan_create(void* stream, const int64_t* rowptr, int64
 
 extern int g_tune_mfma_kperm;   // dense.hip
 extern int g_tune_res_per_cu;
+extern int g_tune_res_grid_cap;
 extern int g_tune_loader_blocks_per_cu;   // gather.hip
 
 DGLL_API int dgll_hip_debug_tune(int key, int value) {
@@ -933,6 +934,7 @@ DGLL_API int dgll_hip_debug_tune(int key, int value) {
         case 9: g_gat_tune.gen = value; break;
         case 11: g_tune_res_per_cu = value; break;
         case 12: g_tune_loader_blocks_per_cu = value; break;
+        case 16: g_tune_res_grid_cap = value; break;
         default: set_error("unknown tuning key"); return DGLL_ERR_INVALID;
     }
     return DGLL_OK;

@@ -47,7 +47,11 @@ const char* dgll_hip_last_error(void);
 int dgll_hip_device_info(int device, char* name, int name_len, int* compute_units, int64_t* global_mem_bytes);
 
 /* Diagnostics only: kernel tuning knobs used by tools/spmm_tune.py (0 unroll depth, 1 rows per wavefront, 2 flags,
- * 3 default long-row threshold).  Not part of the data path; not thread-safe. */
+ * 3 default long-row threshold).  Not part of the data path; not thread-safe.
+ * Key 16: cap on the grid of the resident-weights bf16 transform (gemm_bf16_res_kernel).  0 = no cap (shipped default);
+ * v > 0: min(default grid, max(16, v / 16 * 16)) workgroups -- whole groups of 16, which the pairing of column-split partners
+ * needs.  With 16 a persistent workgroup wraps to its second row block after 16 x 512 rows, so the kernel's steady state is
+ * reachable at test sizes (tests/test_dense_steady_gpu.py); dgll_hip_debug_transform_choice reports the capped grid. */
 int dgll_hip_debug_tune(int key, int value);
 
 /* Diagnostics only, touches no device: the kernel a dgll_hip_spmm_csr* launch of this description gets under the current
@@ -84,6 +88,26 @@ int dgll_hip_debug_gat_choice(int pass, int dtype, int heads, int fo, int mode, 
                               int score_behind_row, int score_pitch_equal, int second_follows, int64_t pad_bytes, int has_plan,
                               int64_t n_rows, int64_t nnz, int64_t n_chunks, int64_t n_long, int y_aligned,
                               struct dgll_gat_choice* out);
+
+/* Diagnostics only, touches no device: the kernel a dgll_hip_transform_bf16* launch of this description gets under the current
+ * knobs (keys 4, 11, 16) -- the launch path calls the same function.  In: N, K1, K2 (0 = no second operand pair); whether an
+ * input ReLU mask, fp32 output, row scale, addend, bf16 out_gate, gate_bits is given; out_aligned: the output is 16-byte
+ * aligned with ldo % 8 == 0; ldw_equal: ldw1 == ldw2; dual: dgll_hip_transform_bf16_dual (K2 and the epilogue inputs are
+ * ignored); M rows; n_cu: the device's compute-unit count (the launch path passes the real one; <= 0 means 256).
+ * Out: kernel 0 = the 4-wave gemm_bf16_nt_kernel<nt> (one 128-row block per workgroup; ntw .. per_cu are 0), 1 = the persistent
+ * resident-weights gemm_bf16_res_kernel<ntw, .., nc, cs, colsplit, .., epi, .., dual>: rows_per_block rows per block, lds_bytes of
+ * dynamic LDS, per_cu workgroups per CU, `workgroups` in the grid, which walk row_sequences (= workgroups / colsplit) interleaved
+ * sequences of the n_blocks row blocks -- a workgroup runs more than one block when n_blocks > row_sequences;
+ * bits_in_epilogue: sign bits asked for (bits_out) are written by the kernel's epilogue (1) or by sign_bits_kernel afterwards (0).
+ * A refusal returns its code (also in `error`) with `message` (static storage) as the error text.                           */
+struct dgll_transform_choice {
+    int kernel, nt, ntw, nc, cs, colsplit, epi, dual, rows_per_block, lds_bytes, per_cu, bits_in_epilogue, error;
+    int64_t workgroups, row_sequences, n_blocks;
+    const char* message;
+};
+int dgll_hip_debug_transform_choice(int N, int K1, int K2, int mask, int out_f32, int row_scale, int addend, int out_gate,
+                                    int gate_bits, int out_aligned, int ldw_equal, int dual, int64_t M, int n_cu,
+                                    struct dgll_transform_choice* out);
 
 /* ---- CSR schedule ----------------------------------------------------------------------------------
  * Built once per adjacency structure (the reference builds its adjacency once per graph,
