@@ -1,5 +1,5 @@
 """Drop-in `dgll` namespace: the reference's import paths (`from dgll import backend as F`,
-`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.sampling.neighbor`, `dgll.dataloader`, `dgll.embedding`, `dgll.community`) resolved onto
+`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.sampling.neighbor`, `dgll.sampling.edge`, `dgll.dataloader`, `dgll.embedding`, `dgll.community`) resolved onto
 the MI355X-native implementation in dgll_amd.  /root/reference/dgll/__init__.py:1 is `import torch as backend`;
 here `backend` is dgll_amd.backend (torch + the missing aliases + HIP aggregation)."""
 import importlib
@@ -26,6 +26,7 @@ _ALIASES = {
     "dgll.sampling.dgllsampler": "dgll_amd.sampling.dgllsampler",
     "dgll.sampling.layerwise": "dgll_amd.sampling.layerwise",
     "dgll.sampling.neighbor": "dgll_amd.sampling.neighbor",
+    "dgll.sampling.edge": "dgll_amd.sampling.edge",
     "dgll.sampling.community": "dgll_amd.sampling.community",
     "dgll.dataloader": "dgll_amd.dataloader",
     "dgll.embedding": "dgll_amd.embedding",

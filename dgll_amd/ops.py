@@ -481,3 +481,4 @@ def cross_entropy(logits, labels, reduction="mean", fold_relu=False):
 
 from .ops_edge import (dropout_seed, gat_aggregate, gat_dropout_mask, gat_layer, head_width_padded, sddmm_raw,  # noqa: E402,F401
                        segment_max)
+from .ops_pair import pair_dot  # noqa: E402,F401

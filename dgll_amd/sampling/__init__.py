@@ -4,3 +4,4 @@ from .fast_sampler import FastNeighborSampler  # noqa: F401
 from .layerwise import FastGCNSampler, FastGCNSamplerFlat, Ladies, LadiesFlatWrs, LadiesWrs, LayerwiseSampler  # noqa: F401
 from .neighbor import NeighborSampler  # noqa: F401
 from .community import CommunityBatchLoader  # noqa: F401
+from .edge import EdgePredictionSampler, PairBatch  # noqa: F401

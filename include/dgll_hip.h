@@ -745,6 +745,48 @@ int dgll_hip_nb_sample_weighted(void* stream, const int64_t* rowptr, const int32
 /* Rows of more entries than this are drawn by a workgroup each, shorter ones by a lane group (dgll_hip_nb_sample_weighted).      */
 int dgll_hip_nb_long_row(void);
 
+/* ---- link prediction: edge batches, negatives, exclusion, pair scores (dgll_amd/sampling/edge.py, dgll_amd/ops_pair.py) -------
+ * The graph is the neighbour sampler's CSR of in-neighbours over n_total < 2^31 nodes with nnz entries; entry e of row v is the edge
+ * col[e] -> v and e is its edge id.  edge_ids int64[n_edges] (duplicates allowed) is one batch; K = negatives >= 0.
+ * pairs int32[pairs_cap >= n_edges * (1 + K), 2] receives GLOBAL (src, dst) ids: row i < n_edges is positive i, (col[e], the row
+ * of e); row n_edges + i * K + k is negative k of positive i, (col[e], c).  c comes from attempts a = 0, 1, ...:
+ * c = mulhi32(x[0], n_total), x = Philox4x32-10 with key = {seed lo, seed hi} and counter = {e lo, e hi, k | 0x40000000, a} (a
+ * domain apart from the neighbour sampler's layer and layer | 0x80000000: one seed may drive both).  filter_existing == 0: attempt
+ * 0 is taken.  Otherwise c is rejected while col[e] occurs in row c (binary search: columns ascending within every row), and
+ * after max_attempts >= 1 rejections the last candidate is kept and counted.  A negative depends on (seed, e, k) only.
+ * Workspaces: mark uint32[n_total] persists per graph (epoch tags: start zeroed, never cleared, a fresh non-zero epoch per call);
+ * bitmap uint32[ceil(n_total / 32)] (cleared here) receives the bit of every endpoint, prefix int32[the same] the set bits below
+ * each word.  info int64[8] (zeroed here) = {distinct endpoints M, capped negatives, error bits: 1 an edge id outside [0, nnz),
+ * 2 a column id outside [0, n_total)}.  The caller reads info once, sizes the outputs and calls dgll_hip_ep_compact.            */
+int dgll_hip_ep_draw(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_total, int64_t nnz, const int64_t* edge_ids,
+                     int64_t n_edges, int negatives, int filter_existing, int max_attempts, uint64_t seed, uint32_t* mark, uint32_t epoch,
+                     uint32_t* bitmap, int32_t* prefix, int32_t* pairs, int64_t pairs_cap, int64_t* info);
+/* output_nodes int64[n_nodes = M]: the distinct endpoints in ascending id order; local_pairs int32[n_pairs, 2]: `pairs` as
+ * positions in output_nodes.  Only after info[2] == 0.                                                                          */
+int dgll_hip_ep_compact(void* stream, int64_t n_total, const uint32_t* bitmap, const int32_t* prefix, int64_t n_nodes,
+                        const int32_t* pairs, int64_t n_pairs, int64_t* output_nodes, int32_t* local_pairs);
+/* Remove from a block (int64 rowptr[n_rows + 1], int32 local col[nnz]; src_nodes int64[n_cols] its sources' global ids, the first
+ * n_rows of them its destinations) every entry a -> b whose key b * n_total + a is in keys int64[n_keys > 0], sorted ascending.
+ * _count: out_rowptr int64[n_rows + 1] = row pointers of the kept entries, info[0] = their number.  _fill (same arguments, that
+ * out_rowptr, out_nnz = info[0]): out_col int32[out_nnz] the kept entries in their order, out_val fp32[out_nnz] = 1 / (kept
+ * entries of the row) or NULL for none.                                                                                         */
+int dgll_hip_ep_exclude_count(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t nnz, const int64_t* src_nodes,
+                              int64_t n_cols, int64_t n_total, const int64_t* keys, int64_t n_keys, int64_t* out_rowptr, int64_t* info);
+int dgll_hip_ep_exclude_fill(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t nnz, const int64_t* src_nodes,
+                             int64_t n_cols, int64_t n_total, const int64_t* keys, int64_t n_keys, const int64_t* out_rowptr, int64_t out_nnz,
+                             int32_t* out_col, float* out_val);
+/* score[p] = <h[pairs[p, 0]], h[pairs[p, 1]]> in fp32.  h: [n_nodes, feat] of `dtype`, base 16-byte aligned, ldh (elements) a
+ * whole number of 16-byte vectors >= feat; the padding of a row may hold anything.  A pair with an id outside [0, n_nodes) scores
+ * NaN and reads nothing.                                                                                                       */
+int dgll_hip_pair_dot(void* stream, const void* h, int64_t ldh, int64_t n_nodes, int feat, int dtype, const int32_t* pairs, int64_t n_pairs,
+                      float* score);
+/* grad_h[i] = sum over e in [inc_rowptr[i], inc_rowptr[i + 1]), in that order, of g[inc_pair[e]] * h[inc_other[e]]: fp32
+ * accumulation, no atomics, written in `dtype` (rows without entries: zeros).  The incidence CSR lists, for node i, every pair
+ * slot that holds i with the pair's other endpoint, ascending by (pair, slot).  grad_h: ldg (elements) a whole number of 16-byte
+ * vectors covering feat rounded up to one; the padding columns are written (zeros).                                             */
+int dgll_hip_pair_dot_bwd(void* stream, const void* h, int64_t ldh, int64_t n_nodes, int feat, int dtype, const int64_t* inc_rowptr,
+                          const int32_t* inc_pair, const int32_t* inc_other, int64_t n_pairs, const float* g, void* grad_h, int64_t ldg);
+
 
 /* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
  * Every random word is Philox4x32-10 with key = {seed lo, seed hi}.
