@@ -1,5 +1,5 @@
 """Drop-in `dgll` namespace: the reference's import paths (`from dgll import backend as F`,
-`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.sampling.neighbor`, `dgll.sampling.edge`, `dgll.dataloader`, `dgll.embedding`, `dgll.community`) resolved onto
+`dgll.nn.Convolution.gcnconv`, `dgll.data.dgraph`, `dgll.sampling.dgllsampler`, `dgll.sampling.neighbor`, `dgll.sampling.edge`, `dgll.sampling.subgraph`, `dgll.dataloader`, `dgll.embedding`, `dgll.community`) resolved onto
 the MI355X-native implementation in dgll_amd.  /root/reference/dgll/__init__.py:1 is `import torch as backend`;
 here `backend` is dgll_amd.backend (torch + the missing aliases + HIP aggregation)."""
 import importlib
@@ -28,6 +28,7 @@ _ALIASES = {
     "dgll.sampling.neighbor": "dgll_amd.sampling.neighbor",
     "dgll.sampling.edge": "dgll_amd.sampling.edge",
     "dgll.sampling.community": "dgll_amd.sampling.community",
+    "dgll.sampling.subgraph": "dgll_amd.sampling.subgraph",
     "dgll.dataloader": "dgll_amd.dataloader",
     "dgll.embedding": "dgll_amd.embedding",
     "dgll.community": "dgll_amd.community",

@@ -203,6 +203,12 @@ SIGNATURES = {
     "dgll_hip_ep_exclude_fill": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "dgll_hip_pair_dot": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
     "dgll_hip_pair_dot_bwd": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64]),
+    "dgll_hip_sg_count": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, C.c_uint32, _vp, _vp]),
+    "dgll_hip_sg_fill": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, C.c_uint32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "dgll_hip_sg_long_row": (_i32, []),
+    "dgll_hip_sg_draw": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i64, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "dgll_hip_sg_walk_nodes": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "dgll_hip_sg_compact": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "dgll_hip_random_walk": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _i32, _vp, _vp]),
     "dgll_host_node2vec_thresholds": (_i32, [C.c_double, C.c_double, _vp]),
     "dgll_hip_alias_build": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),

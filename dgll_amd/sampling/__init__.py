@@ -5,3 +5,4 @@ from .layerwise import FastGCNSampler, FastGCNSamplerFlat, Ladies, LadiesFlatWrs
 from .neighbor import NeighborSampler  # noqa: F401
 from .community import CommunityBatchLoader  # noqa: F401
 from .edge import EdgePredictionSampler, PairBatch  # noqa: F401
+from .subgraph import SAINTSampler, ShaDowKHopSampler, SubgraphWorkspace, node_subgraph  # noqa: F401

@@ -787,6 +787,43 @@ int dgll_hip_pair_dot(void* stream, const void* h, int64_t ldh, int64_t n_nodes,
 int dgll_hip_pair_dot_bwd(void* stream, const void* h, int64_t ldh, int64_t n_nodes, int feat, int dtype, const int64_t* inc_rowptr,
                           const int32_t* inc_pair, const int32_t* inc_other, int64_t n_pairs, const float* g, void* grad_h, int64_t ldg);
 
+/* ---- induced subgraphs and GraphSAINT node sets (dgll_amd/sampling/subgraph.py) ------------------------------------------------
+ * The parent is a square CSR over n_total < 2^31 nodes with nnz entries (int64 rowptr, int32 col, optional fp32 val); its rows need
+ * not be sorted and may hold parallel entries.  nodes int64[m] (distinct, any order) lists the subgraph's nodes: output row i is
+ * parent row nodes[i] restricted to the entries whose column is listed, in the parent's order, each column rewritten to its
+ * position in `nodes`.
+ * Workspace that persists per graph: tag uint64[n_total], epoch << 32 | local id (starts zeroed, never cleared, every call passes a
+ * fresh non-zero epoch).  dgll_hip_sg_count marks the nodes (64-bit atomic exchange), counts the kept entries of every row and scans:
+ * out_rowptr int64[m + 1]; info int64[8] (zeroed here) = {nnz of the subgraph, -, error bits: 1 a node id outside [0, n_total),
+ * 2 a column id outside it, 4 a node listed twice}.  The caller reads info once, sizes the outputs and calls dgll_hip_sg_fill with the
+ * same tags and epoch.  m == 0 is allowed (out_rowptr = {0}).                                                                    */
+int dgll_hip_sg_count(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_total, int64_t nnz, const int64_t* nodes, int64_t m,
+                      uint64_t* tag, uint32_t epoch, int64_t* out_rowptr, int64_t* info);
+/* The entries of that subgraph (out_nnz = info[0]): out_col int32[out_nnz] local ids; out_val fp32[out_nnz] or NULL for none: the
+ * parent's value of the entry when val is given, 1 / (kept entries of the row) when val is NULL; out_eid int64[out_nnz] or NULL:
+ * the parent's entry index of every kept entry.  The kept entries of a row keep the parent's order; two runs give the same bits.
+ * Only after info[2] == 0.                                                                                                       */
+int dgll_hip_sg_fill(void* stream, const int64_t* rowptr, const int32_t* col, const float* val, int64_t n_total, int64_t nnz,
+                     const int64_t* nodes, int64_t m, const uint64_t* tag, uint32_t epoch, const int64_t* out_rowptr, int64_t out_nnz,
+                     int32_t* out_col, float* out_val, int64_t* out_eid, int64_t* info);
+/* Rows of more entries than this are walked by a workgroup each, shorter ones by a lane group (both passes).                      */
+int dgll_hip_sg_long_row(void);
+/* GraphSAINT's draws.  Draw i in [0, budget) makes ONE Philox4x32-10 call with key = {seed lo, seed hi} and counter =
+ * {i lo, i hi, 0, mode}; w = x0 << 32 | x1.  (Counter word 2 is 0; dgll_hip_random_walk uses its step >= 1 there: one seed may drive
+ * both.)  mode 1 (node): e = mulhi64(w, nnz), the node is the row that holds entry e -- in proportion to the row lengths, with
+ * replacement, rows without entries never.  mode 2 (edge): the same e, its row and col[e].  Modes 1 and 2 set the nodes' bits in
+ * bitmap uint32[ceil(n_total / 32)] (cleared here), prefix int32[the same] receives the set bits below each word and info int64[8]
+ * (zeroed here) = {distinct nodes, -, error bits: 2 a column id outside [0, n_total)}; they need nnz > 0.  mode 3 (walk roots):
+ * roots int64[budget], roots[i] = mulhi64(w, n_total); bitmap, prefix and col are not used and may be NULL.                        */
+int dgll_hip_sg_draw(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_total, int64_t nnz, int mode, int64_t budget,
+                     uint64_t seed, uint32_t* bitmap, int32_t* prefix, int64_t* roots, int64_t* info);
+/* The node set of a walk matrix (walks int32[n_entries] of dgll_hip_random_walk; -1 and ids outside [0, n_total) are skipped):
+ * bitmap (cleared here), prefix and info[0] as above.                                                                            */
+int dgll_hip_sg_walk_nodes(void* stream, const int32_t* walks, int64_t n_entries, int64_t n_total, uint32_t* bitmap, int32_t* prefix,
+                           int64_t* info);
+/* out_nodes int64[n_nodes = info[0]]: the set bits in ascending id order.                                                          */
+int dgll_hip_sg_compact(void* stream, int64_t n_total, const uint32_t* bitmap, const int32_t* prefix, int64_t n_nodes, int64_t* out_nodes);
+
 
 /* ---- graph embeddings: random walks and skip-gram with negative sampling (dgll_amd/embedding) -------------------------------
  * Every random word is Philox4x32-10 with key = {seed lo, seed hi}.
