@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 
 
 def np_graph(n, avg_deg, seed, heavy_rows=(), empty_rows=(), weighted=True, n_cols=None):
-    """Random CSR with optional very long rows (> the 512-edge chunk threshold) and forced-empty rows."""
+    """Random CSR with optional very long rows (> the 256-edge chunk threshold) and forced-empty rows."""
     rng = np.random.default_rng(seed)
     n_cols = n if n_cols is None else n_cols
     deg = rng.poisson(avg_deg, n)

@@ -47,7 +47,7 @@ def what(c):
 
 class knobs:
     """dgll_hip_debug_tune(key, value) for the block, the defaults restored in a finally."""
-    DEFAULT = {0: 4, 1: 0, 2: 0, 5: 0, 13: 0, 15: 0}       # the initialisers of SpmmTune (spmm.hip): there is no getter; keep in step
+    DEFAULT = {0: 4, 1: 0, 2: 0, 3: 0, 5: 0, 13: 0, 14: 256, 15: 0}       # the initialisers of SpmmTune (spmm.hip): there is no getter; keep in step
 
     def __init__(self, **kv):
         self.kv = {int(k[1:]): v for k, v in kv.items()}
@@ -272,16 +272,18 @@ def bench():
     return mod
 
 
-def fragment(c, dtype, weighted, extra):
+def fragment(c, dtype, weighted, extra, y_dtype=None):
+    """The instantiation launch_rows() picks for the choice c, as bench.py names it; y_dtype: the output's, where it is not X's."""
     t = "unsigned short" if dtype == BF16 else "float"
+    ty = t if y_dtype is None else ("unsigned short" if y_dtype == BF16 else "float")
     w, e = "true" if weighted else "false", "true" if extra else "false"
     if c.kernel == S:
-        return "spmm_rowslot_kernel<%s, %s, %d, %d, %s, %s>" % (t, t, c.epv, c.lpr, w, e)
+        return "spmm_rowslot_kernel<%s, %s, %d, %d, %s, %s>" % (t, ty, c.epv, c.lpr, w, e)
     if c.kernel == F:
-        return "spmm_csr_flat_kernel<%s, %s, %d, %d, %s, %d, %s>" % (t, t, c.epv, c.lpr, w, c.unroll, e)
+        return "spmm_csr_flat_kernel<%s, %s, %d, %d, %s, %d, %s>" % (t, ty, c.epv, c.lpr, w, c.unroll, e)
     if c.kernel == G:
-        return "spmm_rowgroup_kernel<%s, %s, %d, %d, %d, %s>" % (t, t, c.epv, c.lpr, c.spr, w)
-    return "spmm_csr_kernel<%s, %s, %d, %d, %s, %d, %s, %s>" % (t, t, c.epv, c.lpr, w, c.unroll, e, "true" if c.prefetch else "false")
+        return "spmm_rowgroup_kernel<%s, %s, %d, %d, %d, %s>" % (t, ty, c.epv, c.lpr, c.spr, w)
+    return "spmm_csr_kernel<%s, %s, %d, %d, %s, %d, %s, %s>" % (t, ty, c.epv, c.lpr, w, c.unroll, e, "true" if c.prefetch else "false")
 
 
 def test_agrees_with_the_fragment_bench_names(bench):
