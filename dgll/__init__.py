@@ -18,6 +18,8 @@ _ALIASES = {
     "dgll.nn.Convolution.gatconv": "dgll_amd.nn.Convolution.gatconv",
     "dgll.nn.Convolution.ginconv": "dgll_amd.nn.Convolution.ginconv",
     "dgll.nn.Convolution.gatv2conv": "dgll_amd.nn.Convolution.gatv2conv",
+    "dgll.nn.Convolution.dotgatconv": "dgll_amd.nn.Convolution.dotgatconv",
+    "dgll.nn.Convolution.transformerconv": "dgll_amd.nn.Convolution.transformerconv",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",

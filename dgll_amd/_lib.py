@@ -74,6 +74,20 @@ GATV2_FORWARD, GATV2_ROWS, GATV2_TRANSPOSED = 0, 1, 2
 GATV2_LONG_ROW = 256        # DGLL_GATV2_LONG_ROW of include/dgll_hip.h
 
 
+class AttnDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_attn_desc (dgll_hip_sparse_attn_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("heads", C.c_int), ("D", C.c_int), ("scale", C.c_float), ("kv_shared", C.c_int),
+                ("q", C.c_void_p), ("ld_q", C.c_int64), ("k", C.c_void_p), ("ld_k", C.c_int64), ("v", C.c_void_p), ("ld_v", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("out2", C.c_void_p), ("ld_out2", C.c_int64), ("lse", C.c_void_p), ("lse_delta", C.c_void_p)]
+
+
+ATTN_FORWARD, ATTN_ROWS, ATTN_COLS = 0, 1, 2
+ATTN_LONG_ROW = 256         # DGLL_ATTN_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -248,6 +262,7 @@ SIGNATURES = {
     "dgll_hip_gat_dropout_mask": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, C.c_double, _vp]),
     "dgll_host_gat_dropout_mask": (_i32, [_vp, _vp, _i64, _i32, _vp, C.c_double, _vp]),
     "dgll_hip_gatv2_pass": (_i32, [_vp, C.POINTER(Gatv2Desc)]),
+    "dgll_hip_sparse_attn_pass": (_i32, [_vp, C.POINTER(AttnDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -6,7 +6,9 @@ from .sageconv import NeighborAggregator, sageConv, GraphSage
 from .gatconv import gatConv, sparseGatConv, SpecialSpmm, SpecialSpmmFunction, GAT, SpGAT
 from .ginconv import GinConv, GIN
 from .gatv2conv import GATv2Conv, GATv2
+from .dotgatconv import DotGatConv
+from .transformerconv import TransformerConv, GraphTransformer
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
-           "GATv2Conv", "GATv2"]
+           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer"]

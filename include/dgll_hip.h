@@ -997,6 +997,42 @@ typedef struct dgll_gatv2_desc {
 } dgll_gatv2_desc;
 int dgll_hip_gatv2_pass(void* stream, const dgll_gatv2_desc* d);
 
+/* ---- Sparse scaled dot-product attention: the three gather passes of one layer behind one entry point (csrc/sparse_attn.hip) ------
+ * Per head of width D, over the rows i of a CSR matrix A [n_dst x n_src] (rectangular allowed; edge values are not read, duplicate
+ * entries are separate edges):
+ *     s_ij = scale <q[i], k[j]>     alpha = softmax over row i     out[i] = sum_j alpha_ij v[j]     lse[i] = log sum_j exp s_ij
+ * an empty row gives out[i] = 0 and lse[i] = 0.  `scale` is an argument and is never derived from D (the layers pad D).  Nothing is
+ * stored per edge; the backward passes recompute alpha_ij from lse.  With g = grad_out:
+ *   DGLL_ATTN_FORWARD  rowptr / col = A, n_rows = n_dst, n_cols = n_src.  Reads q, k, v; writes out [n_dst, heads * D] of `dtype` and
+ *                      lse fp32 [n_dst, heads].
+ *   DGLL_ATTN_ROWS     the same A.  Reads q, k, v, grad_out [n_dst, heads * D], lse; writes out = grad_q [n_dst, heads * D] and
+ *                      lse_delta fp32 [n_dst, 2 * heads] ({lse_i | delta_i} side by side per row, delta_i = sum_j alpha_ij <g_i, v_j>
+ *                      formed in fp32).
+ *   DGLL_ATTN_COLS     rowptr / col = A^T, n_rows = n_src, n_cols = n_dst.  Reads q, k, v, grad_out, lse_delta; writes out = grad_k and
+ *                      out2 = grad_v, both [n_src, heads * D] (zeros for a source no row references).
+ * kv_shared != 0: k and v are the same buffer (same pointer and pitch); the forward and the rows pass load each source row once.
+ * The cols pass still writes grad_k and grad_v separately.
+ * Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation), pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned
+ * bases; D a multiple of the vector width (4 fp32 / 8 bf16 columns), at most 64 vectors.  Rows longer than DGLL_ATTN_LONG_ROW
+ * entries are swept by a whole workgroup.  No float atomics: two runs give the same bits.  No pass allocates, synchronises or reads
+ * anything back: the calls can be captured into a graph.                                                                          */
+enum { DGLL_ATTN_FORWARD = 0, DGLL_ATTN_ROWS = 1, DGLL_ATTN_COLS = 2 };
+#define DGLL_ATTN_LONG_ROW 256
+typedef struct dgll_attn_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; int64_t n_rows; int64_t n_cols;
+    int heads; int D; float scale; int kv_shared;
+    const void* q; int64_t ld_q;
+    const void* k; int64_t ld_k;
+    const void* v; int64_t ld_v;
+    const void* grad_out; int64_t ld_grad_out;
+    void* out; int64_t ld_out;
+    void* out2; int64_t ld_out2;
+    float* lse;
+    float* lse_delta;
+} dgll_attn_desc;
+int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d);
+
 #ifdef __cplusplus
 }
 #endif

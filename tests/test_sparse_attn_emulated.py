@@ -1,0 +1,100 @@
+"""csrc/sparse_attn.hip without a GPU: the UNMODIFIED kernel source compiled with g++ against the host stand-ins of tests/gatv2_emu/
+for its two headers and run in lock step (tests/sparse_attn_emu/main.cpp) -- a fiber per lane, 256 per workgroup, wave shuffles and
+__syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against the float64
+restatement of attn_ref.py, at the bars of test_sparse_attn_gpu.py.
+
+It checks what the source says (lane layout, index batches, online softmax, the long-row merge, the three gradients, the shared
+k / v path, bounds and alignment of every access); it cannot check what only the card shows (the exp2 / log instructions, execution
+masks, timing)."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from attn_ref import sparse_attention_reference
+from conftest import ROOT
+
+
+@pytest.fixture(scope="module")
+def emulator(tmp_path_factory):
+    work = tmp_path_factory.mktemp("sparse_attn_emu")
+    for name in ("common.hpp", "edge_args.hpp"):
+        shutil.copy(os.path.join(ROOT, "tests", "gatv2_emu", name), work)
+    shutil.copy(os.path.join(ROOT, "tests", "sparse_attn_emu", "main.cpp"), work)
+    shutil.copy(os.path.join(ROOT, "dgll_amd", "csrc", "sparse_attn.hip"), work)
+    exe = str(work / "sparse_attn_emu")
+    subprocess.run([shutil.which("g++") or "g++", "-O1", "-std=c++17", "-x", "c++", str(work / "main.cpp"), "-I", os.path.join(ROOT, "include"),
+                    "-o", exe], check=True, capture_output=True, text=True)
+    return exe
+
+
+def _graph(full):
+    """full -- 24 x 30: an empty row, one entry, 64, 65, one column five times, LONG_ROW, LONG_ROW + 1 and 400 entries (columns with
+    repetition), short rows, an empty last row; the last source is never referenced.  Not full -- 9 x 12: empty, one entry, LONG_ROW + 1,
+    short rows, empty (the wide case, whose emulation costs most per entry)."""
+    from dgll_amd import CSRGraph, ops_attn
+
+    rng = np.random.RandomState(9)
+    n_src = 30 if full else 12
+    draw = lambda k: list(rng.randint(0, n_src - 1, k))         # noqa: E731
+    if full:
+        rows = [[], [7], draw(64), draw(65), [11] * 5, draw(ops_attn.LONG_ROW), draw(ops_attn.LONG_ROW + 1), draw(400)]
+        rows += [draw(rng.randint(1, 9)) for _ in range(15)] + [[]]
+    else:
+        rows = [[], [7], draw(ops_attn.LONG_ROW + 1)] + [draw(rng.randint(1, 9)) for _ in range(5)] + [[]]
+    rowptr = torch.tensor([0] + list(np.cumsum([len(r) for r in rows])), dtype=torch.int64)
+    return CSRGraph(rowptr, torch.tensor([int(c) for r in rows for c in r], dtype=torch.int32), None, len(rows), n_src)
+
+
+def _dump(t, path):
+    (t.view(torch.int16) if t.dtype == torch.bfloat16 else t).contiguous().numpy().tofile(path)
+
+
+def _read(path, dtype, shape):
+    if dtype == torch.bfloat16:
+        return torch.from_numpy(np.fromfile(path, dtype=np.int16)).view(torch.bfloat16).reshape(shape)
+    return torch.from_numpy(np.fromfile(path, dtype=np.float32)).reshape(shape)
+
+
+# lanes per head / per row: 8 x 16 fp32 = 4 / 32; 3 x 24 bf16 = 3 of 4 / 16 (idle lanes, 4 rows a wavefront); 5 x 8 fp32 = 2 / 16
+# (3 idle heads); 3 x 128 fp32 = 32 / 64 in two column blocks (the second half empty); 1 x 48 bf16 = 6 of 8 / 8
+@pytest.mark.parametrize("heads,D,dtype,shared", [(8, 16, torch.float32, False), (3, 24, torch.bfloat16, True), (5, 8, torch.float32, True),
+                                                  (3, 128, torch.float32, False), (1, 48, torch.bfloat16, False)],
+                         ids=lambda v: str(v).replace("torch.", ""))
+def test_kernel_source_in_lock_step(emulator, tmp_path, heads, D, dtype, shared):
+    graph = _graph(full=D < 128)
+    gen = torch.Generator().manual_seed(heads * 100 + D)
+    F, d, scale = heads * D, str(tmp_path), D ** -0.5
+    q = torch.randn(graph.n_rows, F, generator=gen).to(dtype)
+    k = torch.randn(graph.n_cols, F, generator=gen).to(dtype)
+    v = k if shared else torch.randn(graph.n_cols, F, generator=gen).to(dtype)
+    g = torch.randn(graph.n_rows, F, generator=gen).to(dtype)
+    gt, _ = graph.transpose()
+    for name, t in (("rowptr", graph.rowptr), ("col", graph.col), ("trowptr", gt.rowptr), ("tcol", gt.col), ("q", q), ("k", k), ("v", v),
+                    ("g", g)):
+        _dump(t, os.path.join(d, name + ".bin"))
+    res = subprocess.run([emulator, d, str(graph.n_rows), str(graph.n_cols), str(heads), str(D), "0" if dtype == torch.float32 else "1",
+                          repr(scale), "1" if shared else "0"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "emu ok" in res.stdout, res.stdout + res.stderr
+    got = [_read(os.path.join(d, n + ".bin"), dtype, (rows, F))
+           for n, rows in (("out", graph.n_rows), ("dq", graph.n_rows), ("dk", graph.n_cols), ("dv", graph.n_cols))]
+    q64, k64, v64 = (t.double().requires_grad_() for t in (q, k, v))
+    out, _ = sparse_attention_reference(graph.rowptr, graph.col, q64.view(-1, heads, D), k64.view(-1, heads, D), v64.view(-1, heads, D), scale)
+    out = out.reshape(graph.n_rows, F)
+    want = [out.detach()] + list(torch.autograd.grad(out, (q64, k64, v64), g.double()))
+    for name, a, b in zip(("out", "dq", "dk", "dv"), got, want):
+        a = a.double()
+        assert bool(torch.isfinite(a).all()), name
+        if dtype == torch.float32:
+            assert ((a - b).abs().max() / b.abs().max()).item() <= (1e-4 if name == "out" else 2e-3), name
+        elif name == "out":
+            assert ((a - b).abs().max() / b.abs().max()).item() <= 2e-2, name
+        else:
+            assert ((a - b).norm() / b.norm()).item() <= 1.5e-2, name
+    assert got[0][0].abs().max().item() == 0.0 and got[0][-1].abs().max().item() == 0.0         # the empty rows
+    assert got[2][-1].abs().max().item() == 0.0 and got[3][-1].abs().max().item() == 0.0        # the unreferenced source
+    lse = _read(os.path.join(d, "lse.bin"), torch.float32, (graph.n_rows, heads))
+    assert lse[0].abs().max().item() == 0.0 and bool(torch.isfinite(lse).all())
