@@ -88,6 +88,21 @@ ATTN_FORWARD, ATTN_ROWS, ATTN_COLS = 0, 1, 2
 ATTN_LONG_ROW = 256         # DGLL_ATTN_LONG_ROW of include/dgll_hip.h
 
 
+class TypedDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_typed_desc (dgll_hip_typed_spmm_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("etype", C.c_void_p), ("norm", C.c_void_p),
+                ("n_rows", C.c_int64), ("n_cols", C.c_int64), ("R", C.c_int), ("B", C.c_int), ("F", C.c_int64),
+                ("coeff", C.c_void_p), ("x", C.c_void_p), ("ld_x", C.c_int64), ("dz", C.c_void_p), ("ld_dz", C.c_int64),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("p", C.c_void_p), ("ld_p", C.c_int64)]
+
+
+TYPED_EXPAND, TYPED_CONTRACT, TYPED_EDGE_DOTS = 0, 1, 2
+TYPED_LONG_ROW = 256        # DGLL_TYPED_LONG_ROW of include/dgll_hip.h
+TYPED_COEFF_LDS = 4096      # DGLL_TYPED_COEFF_LDS: the coefficient table is staged in LDS up to this many entries (R * B)
+TYPED_BASIS_BLOCK = 8       # DGLL_TYPED_BASIS_BLOCK: bases a launch block accumulates at the most
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -263,6 +278,7 @@ SIGNATURES = {
     "dgll_host_gat_dropout_mask": (_i32, [_vp, _vp, _i64, _i32, _vp, C.c_double, _vp]),
     "dgll_hip_gatv2_pass": (_i32, [_vp, C.POINTER(Gatv2Desc)]),
     "dgll_hip_sparse_attn_pass": (_i32, [_vp, C.POINTER(AttnDesc)]),
+    "dgll_hip_typed_spmm_pass": (_i32, [_vp, C.POINTER(TypedDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

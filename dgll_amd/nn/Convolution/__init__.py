@@ -8,7 +8,8 @@ from .ginconv import GinConv, GIN
 from .gatv2conv import GATv2Conv, GATv2
 from .dotgatconv import DotGatConv
 from .transformerconv import TransformerConv, GraphTransformer
+from .relgraphconv import RelGraphConv, RGCN
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
-           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer"]
+           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN"]

@@ -189,3 +189,31 @@ def products_like_graph(device, seed=0, n=PRODUCTS_NODES, n_undirected=PRODUCTS_
         perm = torch.randperm(n, generator=gen, device=dev)
         src, dst = perm[src], perm[dst]
     return build_graph(src, dst, n, symmetric=True, self_loops=self_loops, weighted=weighted)
+
+
+def typed_graph(scale, edge_factor=8, num_rels=8, n_classes=4, seed=0, device="cpu", reverse=False, zipf=1.0):
+    """Seeded multi-relational graph for R-GCN: RMAT edges, each with a type drawn from a skewed (Zipf-like, p_r ~ (r + 1)^-zipf)
+    distribution over `num_rels` types.  reverse: every edge (j -> i, r) also gets its reverse (i -> j, r + num_rels), so the graph
+    has 2 * num_rels types.  norm_e = 1 / (number of type-r_e edges into the destination of e): R-GCN's 1 / c_{i, r}.
+
+    Labels depend on WHICH types of neighbour a node has, not on how many neighbours: y_i = the class owning the lowest-numbered
+    class-owning type among the edges into i (type r < n_classes - 1 owns class r + 1; class 0: no such edge).  A model that cannot see
+    edge types cannot fit them; R-GCN can.
+
+    -> dict(src, dst, etypes, norm, num_nodes, num_rels, labels): what ops_typed.typed_graph_from_coo takes, on `device`."""
+    n = 1 << scale
+    s, d = rmat_edges_np(scale, edge_factor << scale, seed)
+    rng = np.random.default_rng(seed + 7919)
+    p = (np.arange(num_rels) + 1.0) ** -float(zipf)
+    r = rng.choice(num_rels, size=s.shape[0], p=p / p.sum())
+    total = num_rels
+    if reverse:
+        s, d, r = np.concatenate([s, d]), np.concatenate([d, s]), np.concatenate([r, r + num_rels])
+        total = 2 * num_rels
+    per = np.bincount(d * total + r, minlength=n * total)                  # edges of type r into node i
+    norm = (1.0 / per[d * total + r]).astype(np.float32)
+    owning = max(min(n_classes - 1, num_rels), 0)
+    has = per.reshape(n, total)[:, :owning] > 0
+    labels = np.where(has.any(1), has.argmax(1) + 1, 0).astype(np.int64) if owning else np.zeros(n, dtype=np.int64)
+    t = lambda a: torch.from_numpy(a).to(device)                           # noqa: E731
+    return {"src": t(s), "dst": t(d), "etypes": t(r.astype(np.int64)), "norm": t(norm), "num_nodes": n, "num_rels": total, "labels": t(labels)}

@@ -1033,6 +1033,41 @@ typedef struct dgll_attn_desc {
 } dgll_attn_desc;
 int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d);
 
+/* ---- Typed-edge basis aggregation (R-GCN / RelGraphConv): three gather passes behind one entry point (csrc/typed_spmm.hip) --------
+ * Every entry e of a CSR matrix A [n_dst x n_src] (rectangular allowed, duplicate entries are separate edges) carries a type
+ * etype[e] in [0, R) and optionally a factor norm[e] (NULL: 1).  With the coefficient table coeff fp32 [R, B] (row-major):
+ *     Z[i, b, :] = sum_{e = (j -> i)} norm[e] * coeff[etype[e], b] * X[j, :]          Z: [n_dst, B * F], basis-major blocks of width F
+ *   DGLL_TYPED_EXPAND     rowptr / col / etype / norm = A, n_rows = n_dst, n_cols = n_src.  Reads x [n_src, F]; writes out = Z
+ *                         [n_dst, B * F] of `dtype` (zeros for an empty row).
+ *   DGLL_TYPED_CONTRACT   rowptr / col = A^T with etype / norm in A^T's entry order, n_rows = n_src, n_cols = n_dst.  Reads dz
+ *                         [n_dst, B * F]; writes out = dX [n_src, F], dX[j] = sum_e norm[e] sum_b coeff[etype[e], b] dz[i_e, b, :]
+ *                         (zeros for a source no row references).
+ *   DGLL_TYPED_EDGE_DOTS  rowptr / col = A.  Reads x [n_src, F] and dz [n_dst, B * F]; writes p fp32 [nnz, ld_p], ld_p = B rounded
+ *                         up to 4: p[e, b] = <x[j_e], dz[i_e, b, :]>, the padding columns zeros.  etype, norm and coeff are not read
+ *                         (norm is NOT applied): grad coeff[r, b] = sum over the entries of type r of norm[e] p[e, b].
+ * Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation), pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned
+ * bases; F a multiple of the vector width (4 fp32 / 8 bf16 columns).  Any B >= 1: bases are taken DGLL_TYPED_BASIS_BLOCK at a time,
+ * more of them re-gather x once per block.  coeff goes through LDS when R * B <= DGLL_TYPED_COEFF_LDS entries, else it is read from
+ * global memory.  The type used for addressing is clamped to [0, R): the caller validates the range (dgll_amd/ops_typed.py does,
+ * once per edge set).  Rows longer than DGLL_TYPED_LONG_ROW entries are swept by a whole workgroup.  No atomics: two runs give the
+ * same bits.  No pass allocates, synchronises or reads anything back: the calls can be captured into a graph.                      */
+enum { DGLL_TYPED_EXPAND = 0, DGLL_TYPED_CONTRACT = 1, DGLL_TYPED_EDGE_DOTS = 2 };
+#define DGLL_TYPED_LONG_ROW 256
+#define DGLL_TYPED_COEFF_LDS 4096
+#define DGLL_TYPED_BASIS_BLOCK 8
+typedef struct dgll_typed_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; const int32_t* etype; const float* norm;
+    int64_t n_rows; int64_t n_cols;
+    int R; int B; int64_t F;
+    const float* coeff;
+    const void* x; int64_t ld_x;
+    const void* dz; int64_t ld_dz;
+    void* out; int64_t ld_out;
+    float* p; int64_t ld_p;
+} dgll_typed_desc;
+int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
