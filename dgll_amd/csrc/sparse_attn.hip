@@ -16,23 +16,17 @@
 //   cols     rows of A^T   holds k_j, v_j; gathers q_i, g_i, {lse_i, delta_i}           -> dv_j = sum_i alpha g_i,
 //                                                                                          dk_j = scale sum_i alpha (d_ij - delta_i) q_i
 //
-// Lane layout, tiles, index batches and the long-row merge are those of gatv2.hip (the skeleton is duplicated on purpose: DESIGN 10):
-// a head owns `lph` adjacent lanes (a power of two >= its D / EPV 16-byte vectors; the lanes past them idle), a row `lpr` lanes (a
-// power of two >= 8 holding `hpb` whole heads), a wavefront 64 / lpr rows at a time.  Rows wider than 64 lanes are cut into column
-// blocks of whole heads over blockIdx.y.  A workgroup takes tiles of 4 * 64 / lpr consecutive rows: every lane group sweeps its own
-// row (indices read lpr at a time, coalesced, and handed round the group), then the rows of the tile longer than kLongRow are taken
-// by the whole workgroup one after another -- lane group k of the 4 * 64 / lpr takes index batches k, k + groups, ... and the partials
-// are merged through LDS in group order by the first group.  No atomics anywhere: two runs give the same bits.
-#include "common.hpp"
+// Lane layout, tiles, index batches and the long-row merge: row_tiles.hpp; heads, lanes of a head and column blocks as in gatv2.hip.
+#include "row_tiles.hpp"
 #include "edge_args.hpp"
 
 namespace dgll {
 namespace sat {
 
 constexpr int kLongRow = DGLL_ATTN_LONG_ROW;   // rows longer than this are swept by a whole workgroup
-constexpr int kMinGroup = 8;                   // lanes per row at least (index batches of at least 8)
-constexpr int64_t kMaxGridX = 1 << 22;         // tiles are taken grid-stride past this
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+using rt::head_sum2;
+using rt::kLn2;
+using rt::kLog2e;
 
 struct Args {
     const int64_t* rowptr;
@@ -50,19 +44,6 @@ struct Args {
     float scale;
 };
 
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
-__device__ __forceinline__ void head_sum2(float& p, float& q, int lph) {
-    for (int off = 1; off < lph; off <<= 1) {
-        p += __shfl_xor(p, off);
-        q += __shfl_xor(q, off);
-    }
-}
-
 template <int KIND, int EPV> struct Parts { static constexpr int N = KIND == 0 ? EPV + 2 : (KIND == 1 ? 2 * EPV + 1 : 2 * EPV); };
 
 // State of one lane (its EPV columns of one head of one row), flat so that the long-row merge can move it through LDS:
@@ -73,10 +54,8 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
     using IO = VecIO<T, EPV>;
     __shared__ float lds[NP * kBlock];
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int lpr = a.lpr, slots = kWave / lpr, groups = kWavesPerBlock * slots;
-    const int sub = lane & (lpr - 1), gbase = lane - sub, gid = wave * slots + lane / lpr;
-    const int hl = sub / a.lph, v = sub - hl * a.lph;
+    const rt::Lanes lanes(a.lpr);
+    const int hl = lanes.sub / a.lph, v = lanes.sub - hl * a.lph;
     const int head = (int)blockIdx.y * a.hpb + hl;
     const bool active = hl < a.hpb && head < a.heads && v < a.vph;
     const int hx = active ? head : 0;
@@ -162,49 +141,38 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
         }
     };
 
-    // entries [b, e) in batches of lpr; this lane group takes batches first, first + stride, ...  Every lane of the wavefront runs
-    // every iteration (the trip counts are the wavefront's maxima), so the hand-round shuffles never meet an idle lane.
-    auto sweep = [&](int64_t b, int64_t e, int first, int stride) {
-        const int total = (int)((e - b + lpr - 1) / lpr);
-        const int mine = first < total ? (total - first + stride - 1) / stride : 0;
-        const int max_batches = wave_max(mine);
-        for (int it = 0; it < max_batches; ++it) {
-            const int64_t k0 = b + ((int64_t)first + (int64_t)it * stride) * lpr;
-            int nb = 0;
-            if (it < mine) nb = e - k0 < lpr ? (int)(e - k0) : lpr;
-            int my_col = 0;
-            if (sub < nb) my_col = a.col[k0 + sub];
-            my_col = min(max(my_col, 0), (int)a.n_cols - 1);      // a corrupt index reads a wrong row, never outside the matrix
-            const int max_nb = wave_max(nb);
-            for (int t = 0; t < max_nb; t += U) {
-                typename IO::raw_t r0[U], r1[U];
-                float lse_c[U], delta_c[U];
-                bool ok[U];
+    // one batch of the row's entries, two entries in flight
+    auto batch = [&](int64_t k0, int nb) {
+        const int my_col = rt::batch_index(a.col, k0, nb, (int)a.n_cols, lanes);
+        const int max_nb = rt::wave_max(nb);
+        for (int t = 0; t < max_nb; t += U) {
+            typename IO::raw_t r0[U], r1[U];
+            float lse_c[U], delta_c[U];
+            bool ok[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t c = __shfl(my_col, gbase + ((t + u) & (lpr - 1)));
-                    ok[u] = t + u < nb;
-                    r0[u] = IO::zero();
-                    r1[u] = IO::zero();
-                    lse_c[u] = delta_c[u] = 0.0f;
-                    if (ok[u] && active) {
-                        if constexpr (KIND == 2) {
-                            r0[u] = IO::load(reinterpret_cast<const T*>(a.q + c * a.pb_q + cb));
-                            r1[u] = IO::load(reinterpret_cast<const T*>(a.g + c * a.pb_g + cb));
-                            lse_c[u] = a.ld2[c * 2 * a.heads + hx];
-                            delta_c[u] = a.ld2[c * 2 * a.heads + a.heads + hx];
-                        } else {
-                            r0[u] = IO::load(reinterpret_cast<const T*>(a.k + c * a.pb_k + cb));
-                            if (!shared) r1[u] = IO::load(reinterpret_cast<const T*>(a.v + c * a.pb_v + cb));
-                        }
-                    }
-                    if constexpr (KIND != 2) {
-                        if (shared) r1[u] = r0[u];          // one load of the source row serves score and value
+            for (int u = 0; u < U; ++u) {
+                const int64_t c = rt::hand_round(my_col, t + u, lanes);
+                ok[u] = t + u < nb;
+                r0[u] = IO::zero();
+                r1[u] = IO::zero();
+                lse_c[u] = delta_c[u] = 0.0f;
+                if (ok[u] && active) {
+                    if constexpr (KIND == 2) {
+                        r0[u] = IO::load(reinterpret_cast<const T*>(a.q + c * a.pb_q + cb));
+                        r1[u] = IO::load(reinterpret_cast<const T*>(a.g + c * a.pb_g + cb));
+                        lse_c[u] = a.ld2[c * 2 * a.heads + hx];
+                        delta_c[u] = a.ld2[c * 2 * a.heads + a.heads + hx];
+                    } else {
+                        r0[u] = IO::load(reinterpret_cast<const T*>(a.k + c * a.pb_k + cb));
+                        if (!shared) r1[u] = IO::load(reinterpret_cast<const T*>(a.v + c * a.pb_v + cb));
                     }
                 }
-#pragma unroll
-                for (int u = 0; u < U; ++u) entry(ok[u], r0[u], r1[u], lse_c[u], delta_c[u]);
+                if constexpr (KIND != 2) {
+                    if (shared) r1[u] = r0[u];          // one load of the source row serves score and value
+                }
             }
+#pragma unroll
+            for (int u = 0; u < U; ++u) entry(ok[u], r0[u], r1[u], lse_c[u], delta_c[u]);
         }
     };
 
@@ -237,50 +205,17 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), o);
     };
 
-    for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const int64_t row0 = tile * groups;
-        {   // rows of at most kLongRow entries: one per lane group
-            const int64_t row = row0 + gid;
-            int64_t b = 0, e = 0;
-            if (row < a.n_rows) { b = a.rowptr[row]; e = a.rowptr[row + 1]; }
-            const bool mine = row < a.n_rows && e - b <= kLongRow;
-            if (!mine) e = b;
-            load_row(mine ? row : 0, mine);
-            sweep(b, e, 0, 1);
-            if (mine) finish(row);
-        }
-        for (int r = 0; r < groups; ++r) {      // longer rows: the whole workgroup, one row after another (all conditions block-uniform)
-            const int64_t row = row0 + r;
-            if (row >= a.n_rows) break;
-            const int64_t b = uniform64(a.rowptr[row]), e = uniform64(a.rowptr[row + 1]);
-            if (e - b <= kLongRow) continue;
-            load_row(row, true);
-            sweep(b, e, gid, groups);
-            __syncthreads();                    // the previous merge has read its partials
-#pragma unroll
-            for (int k = 0; k < NP; ++k) lds[k * kBlock + tid] = st[k];
-            __syncthreads();
-            if (tid < lpr) {                    // the first lane group (sub == tid) merges the others in group order
-                for (int p = 1; p < groups; ++p) {
-                    float o[NP];
-#pragma unroll
-                    for (int k = 0; k < NP; ++k) o[k] = lds[k * kBlock + p * lpr + tid];
-                    if constexpr (KIND == 0) {
-                        const float mn = fmaxf(st[0], o[0]);
-                        const float s0 = st[0] == mn ? 1.0f : __builtin_amdgcn_exp2f(st[0] - mn);
-                        const float s1 = o[0] == mn ? 1.0f : __builtin_amdgcn_exp2f(o[0] - mn);
-                        st[0] = mn;
-#pragma unroll
-                        for (int k = 1; k < NP; ++k) st[k] = fmaf(st[k], s0, o[k] * s1);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < NP; ++k) st[k] += o[k];
-                    }
-                }
-                finish(row);
-            }
-        }
-    }
+    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
+        load_row(row, mine);
+        rt::for_each_batch(b, e, 0, 1, lanes, batch);
+        if (mine) finish(row);
+    };
+    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
+        load_row(row, true);
+        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
+        rt::merge_partials<KIND == 0>(st, lds, lanes, [&] { finish(row); });
+    };
+    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
 }
 
 template <typename T>
@@ -299,31 +234,24 @@ DGLL_API int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d) {
     DGLL_REQUIRE(d != nullptr, "the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_ATTN_FORWARD || d->pass == DGLL_ATTN_ROWS || d->pass == DGLL_ATTN_COLS,
                  "pass must be DGLL_ATTN_FORWARD, DGLL_ATTN_ROWS or DGLL_ATTN_COLS");
-    DGLL_REQUIRE(d->dtype == DGLL_F32 || d->dtype == DGLL_BF16, "dtype must be DGLL_F32 or DGLL_BF16");
+    if (const int rc = rt::require_head_pass(d->dtype, d->heads, d->D, d->n_rows, d->n_cols, d->rowptr, d->col)) return rc;
     const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-    DGLL_REQUIRE(d->heads >= 1 && d->D >= epv && d->D % epv == 0,
-                 "heads >= 1 and D a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns)");
-    DGLL_REQUIRE(d->D / epv <= kWave, "a head may span at most 64 vectors (D <= 256 fp32, 512 bf16)");
-    DGLL_REQUIRE((int64_t)d->heads * d->D < (1 << 20), "heads * D < 2^20");
-    DGLL_REQUIRE(d->n_rows >= 0 && d->n_rows < (1ll << 31) && d->n_cols > 0 && d->n_cols < (1ll << 31),
-                 "row count in [0, 2^31), gathered row count in [1, 2^31)");
-    DGLL_REQUIRE(d->rowptr && d->col, "the CSR arrays must be non-NULL");
     DGLL_REQUIRE(d->q && d->k && d->v && d->out, "q, k, v and the pass's output matrix must be non-NULL");
     const int64_t feat = (int64_t)d->heads * d->D;
-    DGLL_REQUIRE(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->out) && d->ld_q % epv == 0 && d->ld_k % epv == 0 &&
-                     d->ld_v % epv == 0 && d->ld_out % epv == 0 && d->ld_q >= feat && d->ld_k >= feat && d->ld_v >= feat && d->ld_out >= feat,
+    DGLL_REQUIRE(rt::require_matrix(d->q, d->ld_q, epv, feat) && rt::require_matrix(d->k, d->ld_k, epv, feat) &&
+                     rt::require_matrix(d->v, d->ld_v, epv, feat) && rt::require_matrix(d->out, d->ld_out, epv, feat),
                  "q, k, v and the output: 16-byte aligned base, a pitch of whole 16-byte vectors >= heads * D");
     DGLL_REQUIRE(!d->kv_shared || (d->k == d->v && d->ld_k == d->ld_v), "kv_shared: k and v must be the same buffer with the same pitch");
     if (d->pass == DGLL_ATTN_FORWARD) {
         DGLL_REQUIRE(d->lse != nullptr, "forward: lse must be non-NULL");
     } else {
-        DGLL_REQUIRE(d->grad_out && aligned16(d->grad_out) && d->ld_grad_out % epv == 0 && d->ld_grad_out >= feat,
+        DGLL_REQUIRE(rt::require_matrix(d->grad_out, d->ld_grad_out, epv, feat),
                      "backward: grad_out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
         DGLL_REQUIRE(d->lse_delta != nullptr, "backward: lse_delta must be non-NULL");
         if (d->pass == DGLL_ATTN_ROWS) {
             DGLL_REQUIRE(d->lse != nullptr, "rows pass: lse must be non-NULL");
         } else {
-            DGLL_REQUIRE(d->out2 && aligned16(d->out2) && d->ld_out2 % epv == 0 && d->ld_out2 >= feat,
+            DGLL_REQUIRE(rt::require_matrix(d->out2, d->ld_out2, epv, feat),
                          "cols pass: out2 (dv) non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
         }
     }
@@ -346,18 +274,15 @@ DGLL_API int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d) {
     a.D = d->D;
     a.scale = d->scale;
     a.kv_shared = d->kv_shared ? 1 : 0;
-    a.vph = d->D / epv;
-    a.lph = 1;
-    while (a.lph < a.vph) a.lph <<= 1;
-    a.hpb = kWave / a.lph < d->heads ? kWave / a.lph : d->heads;       // whole heads per column block
-    a.lpr = sat::kMinGroup;
-    while (a.lpr < a.hpb * a.lph) a.lpr <<= 1;
-    const int groups = kWavesPerBlock * (kWave / a.lpr);
-    a.tiles = (d->n_rows + groups - 1) / groups;
-    const int64_t gx = a.tiles < sat::kMaxGridX ? a.tiles : sat::kMaxGridX;
-    if (gx == 0) return DGLL_OK;
-    DGLL_REQUIRE((d->heads + a.hpb - 1) / a.hpb <= 65535, "at most 65535 column blocks of whole heads");
-    const dim3 grid((unsigned)gx, (unsigned)((d->heads + a.hpb - 1) / a.hpb));
+    const rt::HeadGeometry geo = rt::make_head_geometry(d->heads, d->D, epv, d->n_rows);
+    a.vph = geo.vph;
+    a.lph = geo.lph;
+    a.hpb = geo.hpb;
+    a.lpr = geo.lpr;
+    a.tiles = geo.tiles;
+    if (geo.grid == 0) return DGLL_OK;
+    DGLL_REQUIRE(geo.col_blocks <= 65535, "at most 65535 column blocks of whole heads");
+    const dim3 grid((unsigned)geo.grid, (unsigned)geo.col_blocks);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->dtype == DGLL_F32) sat::launch<float>(d->pass, grid, st, a);
     else sat::launch<bf16_t>(d->pass, grid, st, a);

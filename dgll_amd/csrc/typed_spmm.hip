@@ -11,19 +11,15 @@
 //   contract  rows of A^T   gathers dZ[i, 0 : B F] (etype / norm in A^T's entry order)       -> dX[j, :] = sum_e norm_e sum_b C[r_e, b] dZ[i_e, b, :]
 //   dots      rows of A     holds dZ[i, :, :]; gathers x_j                                   -> P[e, b] = <x_j, dZ[i, b, :]>  (fp32, norm NOT applied)
 //
-// Lane layout, tiles, index batches and the long-row merge are those of sparse_attn.hip: a lane owns one 16-byte vector of columns, a
-// row `lpr` adjacent lanes (a power of two >= 8 and >= its F / EPV vectors; the lanes past them idle), a wavefront 64 / lpr rows at a
-// time.  Rows wider than 64 lanes are cut into column blocks of 64 vectors over blockIdx.y (expand, contract) or swept block after
-// block by the same lanes (dots: a dot product spans the blocks, and the lane that wrote P[e, b] adds the next block's share to it).
-// Bases are taken kBasisBlock or fewer at a time (compile-time block sizes 1, 2, 4, 8: BB x EPV accumulators per lane, in registers);
-// more bases are further blocks over blockIdx.z, each of which gathers x_j again.  A workgroup takes tiles of 4 * 64 / lpr consecutive
-// rows: every lane group sweeps its own row (indices, types and norms read lpr at a time, coalesced, and handed round the group),
-// then the rows of the tile longer than kLongRow are taken by the whole workgroup one after another -- lane group k takes index
-// batches k, k + groups, ... and the partial sums are merged through LDS in group order by the first group, kMergeSlice floats of
-// the state at a time.  The coefficient table is staged in LDS when its R * B entries fit kCoeffLds floats and read from global
-// memory (L2-resident) otherwise.  The type used for addressing is clamped to [0, R) and the column to [0, n_cols): a corrupt buffer
-// gives a wrong number, not a fault.  No atomics anywhere: two runs give the same bits.
-#include "common.hpp"
+// Lane layout, tiles, index batches and the long-row merge: row_tiles.hpp.  Here a row's `lpr` lanes are at least its F / EPV vectors,
+// and a batch hands round types and norms with the indices.  Rows wider than 64 lanes are cut into column blocks of 64 vectors over
+// blockIdx.y (expand, contract) or swept block after block by the same lanes (dots: a dot product spans the blocks, and the lane
+// that wrote P[e, b] adds the next block's share to it).  Bases are taken kBasisBlock or fewer at a time (compile-time block sizes
+// 1, 2, 4, 8: BB x EPV accumulators per lane, in registers); more bases are further blocks over blockIdx.z, each of which gathers
+// x_j again.  The long-row merge moves kMergeSlice floats of the state at a time.  The coefficient table is staged in LDS when its
+// R * B entries fit kCoeffLds floats and read from global memory (L2-resident) otherwise.  The type used for addressing is clamped
+// to [0, R) and the column to [0, n_cols): a corrupt buffer gives a wrong number, not a fault.
+#include "row_tiles.hpp"
 #include "edge_args.hpp"
 
 namespace dgll {
@@ -33,8 +29,6 @@ constexpr int kLongRow = DGLL_TYPED_LONG_ROW;       // rows longer than this are
 constexpr int kCoeffLds = DGLL_TYPED_COEFF_LDS;     // the coefficient table goes through LDS when R * B <= this many floats (16 KB)
 constexpr int kBasisBlock = DGLL_TYPED_BASIS_BLOCK; // bases per launch block at the most
 constexpr int kMergeSlice = 16;                     // floats of a lane's state that cross LDS at a time in the long-row merge (16 KB)
-constexpr int kMinGroup = 8;                        // lanes per row at least (index batches of at least 8)
-constexpr int64_t kMaxGridX = 1 << 22;              // tiles are taken grid-stride past this
 
 struct Args {
     const int64_t* rowptr;
@@ -51,12 +45,6 @@ struct Args {
     int R, B, vpr, lpr, chunks, staged;     // vpr: 16-byte vectors of F columns; chunks: column blocks of lpr vectors (dots)
 };
 
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
 // KIND 0 expand, 1 contract, 2 dots.  BB: bases of this block (contract: unused, 1).  State of one lane, flat so that the long-row
 // merge can move it through LDS: expand st[k * EPV + d] = Z[row, b0 + k, lane's column d]; contract st[d] = dX[row, lane's column d].
 template <typename T, int KIND, int BB>
@@ -66,9 +54,8 @@ __global__ __launch_bounds__(kBlock) void typed_spmm_kernel(const Args a) {
     __shared__ float tab[KIND == 2 ? 1 : kCoeffLds];
     __shared__ float lds[KIND == 2 ? 1 : MS * kBlock];
 
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int lpr = a.lpr, slots = kWave / lpr, groups = kWavesPerBlock * slots;
-    const int sub = lane & (lpr - 1), gbase = lane - sub, gid = wave * slots + lane / lpr;
+    const rt::Lanes lanes(a.lpr);
+    const int tid = lanes.tid, lpr = lanes.lpr, groups = lanes.groups, sub = lanes.sub, gid = lanes.gid;
     const int B = a.B, b0 = KIND == 1 ? 0 : (int)blockIdx.z * BB;
     const int nbk = B - b0 < BB ? B - b0 : BB;              // bases of this block that exist
     const bool staged = a.staged != 0;
@@ -109,12 +96,12 @@ __global__ __launch_bounds__(kBlock) void typed_spmm_kernel(const Args a) {
         }
     };
 
-    // entries [b, e) in batches of lpr; this lane group takes batches first, first + stride, ...  Every lane of the wavefront runs
-    // every iteration (the trip counts are the wavefront's maxima), so the hand-round shuffles never meet an idle lane.
+    // the row's entries [b, e), the batches first, first + stride, ... of them, two entries in flight.  rt::for_each_batch written out:
+    // through the header the loop's branches come out inverted, and CONTRACT measured 2.7 % slower at one shape.
     auto sweep = [&](int64_t b, int64_t e, int first, int stride, bool first_chunk) {
         const int total = (int)((e - b + lpr - 1) / lpr);
         const int mine = first < total ? (total - first + stride - 1) / stride : 0;
-        const int max_batches = wave_max(mine);
+        const int max_batches = rt::wave_max(mine);
         for (int it = 0; it < max_batches; ++it) {
             const int64_t k0 = b + ((int64_t)first + (int64_t)it * stride) * lpr;
             int nb = 0;
@@ -128,9 +115,9 @@ __global__ __launch_bounds__(kBlock) void typed_spmm_kernel(const Args a) {
                     my_w = a.norm ? a.norm[k0 + sub] : 1.0f;
                 }
             }
-            my_col = min(max(my_col, 0), (int)a.n_cols - 1);    // a corrupt index reads a wrong row, never outside the matrix
-            my_type = min(max(my_type, 0), a.R - 1) * B;        // ... and a corrupt type a wrong row of C, never outside it
-            const int max_nb = wave_max(nb);
+            my_col = rt::clamp_index(my_col, (int)a.n_cols);
+            my_type = rt::clamp_index(my_type, a.R) * B;        // a corrupt type: a wrong row of C, never outside it
+            const int max_nb = rt::wave_max(nb);
             for (int t = 0; t < max_nb; t += U) {
                 int64_t c[U];
                 int ty[U];
@@ -138,14 +125,13 @@ __global__ __launch_bounds__(kBlock) void typed_spmm_kernel(const Args a) {
                 bool ok[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const int src = gbase + ((t + u) & (lpr - 1));
-                    c[u] = __shfl(my_col, src);
+                    c[u] = rt::hand_round(my_col, t + u, lanes);
                     ok[u] = t + u < nb;
                     ty[u] = 0;
                     w[u] = 0.0f;
                     if constexpr (KIND != 2) {
-                        ty[u] = __shfl(my_type, src);
-                        w[u] = __shfl(my_w, src);
+                        ty[u] = rt::hand_round(my_type, t + u, lanes);
+                        w[u] = rt::hand_round(my_w, t + u, lanes);
                     }
                 }
                 if constexpr (KIND == 1) {
@@ -230,6 +216,8 @@ __global__ __launch_bounds__(kBlock) void typed_spmm_kernel(const Args a) {
     };
 
     const int ch0 = KIND == 2 ? 0 : (int)blockIdx.y, ch1 = KIND == 2 ? a.chunks : ch0 + 1;
+    // The tile loop and the long-row merge are rt::for_each_tile and rt::merge_partials written out, with the chunk loop between tile
+    // and rows and the state crossing LDS in slices: called through the header, these kernels' register counts move.
     for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
         const int64_t row0 = tile * groups;
         for (int ch = ch0; ch < ch1; ++ch) {
@@ -317,15 +305,15 @@ DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
     const bool dots = d->pass == DGLL_TYPED_EDGE_DOTS, contract = d->pass == DGLL_TYPED_CONTRACT;
     if (!dots) {
         DGLL_REQUIRE(d->etype && d->coeff, "dgll_hip_typed_spmm_pass: expand / contract: etype and coeff must be non-NULL");
-        DGLL_REQUIRE(d->out && aligned16(d->out) && d->ld_out % epv == 0 && d->ld_out >= (contract ? d->F : wide),
+        DGLL_REQUIRE(rt::require_matrix(d->out, d->ld_out, epv, contract ? d->F : wide),
                      "dgll_hip_typed_spmm_pass: out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= its width (expand B * F, contract F)");
     }
     if (!contract) {
-        DGLL_REQUIRE(d->x && aligned16(d->x) && d->ld_x % epv == 0 && d->ld_x >= d->F,
+        DGLL_REQUIRE(rt::require_matrix(d->x, d->ld_x, epv, d->F),
                      "dgll_hip_typed_spmm_pass: x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= F");
     }
     if (d->pass != DGLL_TYPED_EXPAND) {
-        DGLL_REQUIRE(d->dz && aligned16(d->dz) && d->ld_dz % epv == 0 && d->ld_dz >= wide,
+        DGLL_REQUIRE(rt::require_matrix(d->dz, d->ld_dz, epv, wide),
                      "dgll_hip_typed_spmm_pass: dz non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= B * F");
     }
     if (dots) {
@@ -353,13 +341,12 @@ DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
     a.R = d->R;
     a.B = d->B;
     a.vpr = (int)vpr;
-    a.lpr = typed::kMinGroup;
-    while (a.lpr < kWave && a.lpr < vpr) a.lpr <<= 1;
+    const rt::HeadGeometry geo = rt::make_row_geometry(rt::pow2_at_least(vpr < kWave ? vpr : kWave, rt::kMinGroup), d->n_rows);
+    a.lpr = geo.lpr;
+    a.tiles = geo.tiles;
     a.chunks = (int)((vpr + a.lpr - 1) / a.lpr);
     a.staged = (int64_t)d->R * d->B <= typed::kCoeffLds ? 1 : 0;
-    const int groups = kWavesPerBlock * (kWave / a.lpr);
-    a.tiles = (d->n_rows + groups - 1) / groups;
-    const int64_t gx = a.tiles < typed::kMaxGridX ? a.tiles : typed::kMaxGridX;
+    const int64_t gx = geo.grid;
     if (gx == 0) return DGLL_OK;
     // bases per block: the smallest compiled size that holds B, kBasisBlock for more
     int bb = 1;

@@ -1,8 +1,9 @@
-// Host stand-in for csrc/common.hpp: what csrc/gatv2.hip needs to compile with plain g++ and run in LOCK STEP on the CPU
-// (tests/test_gatv2_emulated.py).  A workgroup is 256 fibers (ucontext), one per lane, scheduled round-robin; __shfl / __shfl_xor /
-// readfirstlane are wave-level collectives and __syncthreads a workgroup-level one: a collective that not every lane reaches, a
-// readfirstlane of a value that differs between lanes, and a 16-byte access to an unaligned address end the run with a message.
-// The kernel source is compiled UNMODIFIED (copied next to this file so that its `#include "common.hpp"` finds this one).
+// Host stand-in for csrc/common.hpp: what csrc/row_tiles.hpp and the kernel files on it (gatv2.hip, sparse_attn.hip, typed_spmm.hip)
+// need to compile with plain g++ and run in LOCK STEP on the CPU (tests/kernel_emu.py).  A workgroup is 256 fibers (ucontext), one per
+// lane, scheduled round-robin; __shfl / __shfl_xor / readfirstlane are wave-level collectives and __syncthreads a workgroup-level one: a
+// collective that not every lane reaches, a readfirstlane of a value that differs between lanes, and a 16-byte access to an unaligned
+// address end the run with a message.  The kernel source and row_tiles.hpp are compiled UNMODIFIED (copied next to this file so that
+// their `#include "common.hpp"` finds this one); the definitions are in emu_runtime.hpp.
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -1,4 +1,4 @@
-// Host stand-in for csrc/edge_args.hpp: the two helpers gatv2.hip takes from it.
+// Host stand-in for csrc/edge_args.hpp: the two helpers the attention kernels take from it.
 #pragma once
 #include "common.hpp"
 namespace dgll {

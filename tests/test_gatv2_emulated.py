@@ -1,31 +1,24 @@
-"""csrc/gatv2.hip without a GPU: the UNMODIFIED kernel source compiled with g++ against host stand-ins for its two headers
-(tests/gatv2_emu/) and run in lock step -- a fiber per lane, 256 per workgroup, wave shuffles and __syncthreads as collectives that
-fail when a lane does not reach them -- against the float64 restatement of test_gatv2_host.py, at the bars of test_gatv2_gpu.py.
+"""csrc/gatv2.hip without a GPU: the kernel source and csrc/row_tiles.hpp, both UNMODIFIED, compiled with g++ against host stand-ins
+for common.hpp and edge_args.hpp (tests/kernel_emu/) and run in lock step -- a fiber per lane, 256 per workgroup, wave shuffles and
+__syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against the float64
+restatement of test_gatv2_host.py, at the bars of test_gatv2_gpu.py.
 
 It checks what the source says (lane layout, index batches, online softmax, the long-row merge, the three gradients, bounds and
 alignment of every access); it cannot check what only the card shows (the exp2 / log instructions, execution masks, timing)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from kernel_emu import build_emulator
 from test_gatv2_host import gatv2_reference
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    work = tmp_path_factory.mktemp("gatv2_emu")
-    for name in ("common.hpp", "edge_args.hpp", "main.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "gatv2_emu", name), work)
-    shutil.copy(os.path.join(ROOT, "dgll_amd", "csrc", "gatv2.hip"), work)
-    exe = str(work / "gatv2_emu")
-    subprocess.run([shutil.which("g++") or "g++", "-O1", "-std=c++17", "-x", "c++", str(work / "main.cpp"), "-I", os.path.join(ROOT, "include"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    return exe
+    return build_emulator(tmp_path_factory, "gatv2.hip", "gatv2_main.cpp")
 
 
 def _graph(full):

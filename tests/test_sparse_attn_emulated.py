@@ -1,13 +1,12 @@
-"""csrc/sparse_attn.hip without a GPU: the UNMODIFIED kernel source compiled with g++ against the host stand-ins of tests/gatv2_emu/
-for its two headers and run in lock step (tests/sparse_attn_emu/main.cpp) -- a fiber per lane, 256 per workgroup, wave shuffles and
-__syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against the float64
-restatement of attn_ref.py, at the bars of test_sparse_attn_gpu.py.
+"""csrc/sparse_attn.hip without a GPU: the kernel source and csrc/row_tiles.hpp, both UNMODIFIED, compiled with g++ against host
+stand-ins for common.hpp and edge_args.hpp (tests/kernel_emu/) and run in lock step -- a fiber per lane, 256 per workgroup, wave
+shuffles and __syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against
+the float64 restatement of attn_ref.py, at the bars of test_sparse_attn_gpu.py.
 
 It checks what the source says (lane layout, index batches, online softmax, the long-row merge, the three gradients, the shared
 k / v path, bounds and alignment of every access); it cannot check what only the card shows (the exp2 / log instructions, execution
 masks, timing)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,20 +14,12 @@ import pytest
 import torch
 
 from attn_ref import sparse_attention_reference
-from conftest import ROOT
+from kernel_emu import build_emulator
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    work = tmp_path_factory.mktemp("sparse_attn_emu")
-    for name in ("common.hpp", "edge_args.hpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "gatv2_emu", name), work)
-    shutil.copy(os.path.join(ROOT, "tests", "sparse_attn_emu", "main.cpp"), work)
-    shutil.copy(os.path.join(ROOT, "dgll_amd", "csrc", "sparse_attn.hip"), work)
-    exe = str(work / "sparse_attn_emu")
-    subprocess.run([shutil.which("g++") or "g++", "-O1", "-std=c++17", "-x", "c++", str(work / "main.cpp"), "-I", os.path.join(ROOT, "include"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    return exe
+    return build_emulator(tmp_path_factory, "sparse_attn.hip", "sparse_attn_main.cpp")
 
 
 def _graph(full):

@@ -1,33 +1,24 @@
-"""csrc/typed_spmm.hip without a GPU: the UNMODIFIED kernel source compiled with g++ against the host stand-ins of tests/gatv2_emu/
-for its two headers and run in lock step (tests/typed_spmm_emu/main.cpp) -- a fiber per lane, 256 per workgroup, wave shuffles and
-__syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against the float64
-restatement of typed_ref.py, at the project's bars.
+"""csrc/typed_spmm.hip without a GPU: the kernel source and csrc/row_tiles.hpp, both UNMODIFIED, compiled with g++ against host
+stand-ins for common.hpp and edge_args.hpp (tests/kernel_emu/) and run in lock step -- a fiber per lane, 256 per workgroup, wave
+shuffles and __syncthreads as collectives that fail when a lane does not reach them, every buffer ending at a guard page -- against
+the float64 restatement of typed_ref.py, at the project's bars.
 
 It checks what the source says (lane layout, index batches, basis blocks, the coefficient table, the long-row merge, the dot
 products' butterfly, bounds and alignment of every access); it cannot check what only the card shows (execution masks, LDS, timing)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from kernel_emu import build_emulator
 from typed_ref import edge_dots_reference, typed_spmm_reference
 
 
 @pytest.fixture(scope="module")
 def emulator(tmp_path_factory):
-    work = tmp_path_factory.mktemp("typed_spmm_emu")
-    for name in ("common.hpp", "edge_args.hpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "gatv2_emu", name), work)
-    shutil.copy(os.path.join(ROOT, "tests", "typed_spmm_emu", "main.cpp"), work)
-    shutil.copy(os.path.join(ROOT, "dgll_amd", "csrc", "typed_spmm.hip"), work)
-    exe = str(work / "typed_spmm_emu")
-    subprocess.run([shutil.which("g++") or "g++", "-O1", "-std=c++17", "-x", "c++", str(work / "main.cpp"), "-I", os.path.join(ROOT, "include"),
-                    "-o", exe], check=True, capture_output=True, text=True)
-    return exe
+    return build_emulator(tmp_path_factory, "typed_spmm.hip", "typed_spmm_main.cpp")
 
 
 def _graph(full, R):
