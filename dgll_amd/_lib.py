@@ -60,6 +60,27 @@ class TransformChoice(C.Structure):
                [("workgroups", C.c_int64), ("row_sequences", C.c_int64), ("n_blocks", C.c_int64), ("message", C.c_char_p)]
 
 
+class GatDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_gat_desc (dgll_hip_gat_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int), ("mode", C.c_int), ("apply_elu", C.c_int),
+                ("plan", C.c_void_p), ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64),
+                ("n_cols", C.c_int64), ("heads", C.c_int), ("fo", C.c_int), ("alpha", C.c_float),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("edge_scale", C.c_void_p),
+                ("drop_p", C.c_double), ("drop_seed", C.c_void_p),
+                ("h", C.c_void_p), ("ld_h", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("dn", C.c_void_p), ("ld_dn", C.c_int64),
+                ("grad_h", C.c_void_p), ("ld_grad_h", C.c_int64),
+                ("row_score", C.c_void_p), ("col_score", C.c_void_p), ("col_score_stride", C.c_int), ("col_dd", C.c_void_p),
+                ("attn1", C.c_void_p), ("attn2", C.c_void_p), ("grad_s_rows", C.c_void_p), ("rowsum", C.c_void_p), ("rowmax", C.c_void_p),
+                ("dd", C.c_void_p), ("sd", C.c_void_p), ("sd_stride", C.c_int), ("grad_score", C.c_void_p), ("partial3", C.c_void_p),
+                ("raw", C.c_int), ("accumulate", C.c_int), ("phase", C.c_int)]
+
+
+GAT_FORWARD, GAT_ROWS, GAT_TRANSPOSED = 0, 1, 2
+GAT_ROWS_STORED_FIRST, GAT_ROWS_STORED_FURTHER, GAT_ROWS_EXACT_ONLY = 0, 1, 3       # DGLL_GAT_ROWS_*: the rows pass's `phase`
+GAT_ROWS_EXACT_FIRST, GAT_ROWS_EXACT_MIDDLE, GAT_ROWS_EXACT_LAST = 4, 5, 6
+
+
 class Gatv2Desc(C.Structure):
     """include/dgll_hip.h: struct dgll_gatv2_desc (dgll_hip_gatv2_pass)."""
     _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
@@ -146,38 +167,12 @@ SIGNATURES = {
     "dgll_hip_sage_fused_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32,
                                            _vp, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _sz]),
     "dgll_hip_sddmm_csr": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i32]),
-    "dgll_hip_gat_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32,
-                                C.c_float, _i32, _i32, _vp, _sz]),
-    "dgll_hip_gat_fwd_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32,
-                                   C.c_float, _i32, _vp, _sz, _i32, _i32]),
-    "dgll_hip_gat_bwd_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp,
-                                     _i64, _vp, _vp, _i64, _i32, _i32, C.c_float, _i32, _i32, _i32, _vp, _sz]),
-    "dgll_hip_gat_bwd_rows_split": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp,
-                                           _i64, _i32, _i32, C.c_float, _i32, _i32, _vp, _vp, _sz]),
-    "dgll_hip_gat_bwd_cols": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                                     _i32, _i64, _i32, _i32, C.c_float, _i32, _vp, _sz]),
-    "dgll_hip_gat_fwd_strided": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32,
-                                        C.c_float, _i32, _vp, _sz]),
     "dgll_host_sampler_pool_create": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, C.c_uint64, C.c_uint64, _i32, _i32, _vp, _i64,
                                              _i64, _vp, _vp, _vp, _i32]),
     "dgll_host_sampler_pool_next": (_i32, [_vp, _vp, _vp]),
     "dgll_host_sampler_pool_release": (_i32, [_vp, _i32]),
     "dgll_host_sampler_pool_destroy": (_i32, [_vp]),
-    "dgll_hip_gat_fwd_rowscore": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, C.c_float, _i32,
-                                         _vp, _sz, _i32, _i32]),
-    "dgll_hip_gat_bwd_rows_rowscore": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64,
-                                              _vp, _i32, _vp, _i64, _i64, _i32, _i32, C.c_float, _i32, _vp, _sz]),
-    "dgll_hip_gat_bwd_rows_strided": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64,
-                                             _vp, _i32, _vp, _i64, _i32, _i32, C.c_float, _i32, _vp, _sz]),
-    "dgll_hip_gat_bwd_cols_strided": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i32, _i64,
-                                             _i32, _i32, C.c_float, _vp, _sz, _vp, _vp, _vp]),
-    "dgll_hip_gat_bwd_strided": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64,
-                                        _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, C.c_float,
-                                        _i32, _vp, _sz]),
     "dgll_hip_gat_workspace_bytes": (_sz, [_vp, _i32, _i32]),
-    "dgll_hip_gat_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32,
-                                _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, C.c_float, _i32,
-                                _i32, _vp, _sz]),
     "dgll_hip_gather_rows": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
     "dgll_hip_pack_weight_bf16": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _i32]),
     "dgll_hip_gather_rows_mapped": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
@@ -268,14 +263,9 @@ SIGNATURES = {
                                      _vp, _sz, _vp, _vp]),
     "dgll_hip_louvain_scratch_bytes": (_sz, [_i64, _i64]),
     "dgll_hip_leiden_refine": (_i32, [_vp] * 12 + [_i64, _i64, _i64, C.c_double, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "dgll_hip_gat_fwd_dropout": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32,
-                                        C.c_float, _i32, _vp, _sz, C.c_double, _vp]),
-    "dgll_hip_gat_bwd_rows_dropout": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64,
-                                             _vp, _i32, _vp, _i64, _i64, _i32, _i32, C.c_float, _i32, _vp, _sz, C.c_double, _vp]),
-    "dgll_hip_gat_bwd_cols_dropout": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i32, _i64,
-                                             _i32, _i32, C.c_float, _vp, _sz, _vp, _vp, _vp, C.c_double, _vp]),
     "dgll_hip_gat_dropout_mask": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, C.c_double, _vp]),
     "dgll_host_gat_dropout_mask": (_i32, [_vp, _vp, _i64, _i32, _vp, C.c_double, _vp]),
+    "dgll_hip_gat_pass": (_i32, [_vp, C.POINTER(GatDesc)]),
     "dgll_hip_gatv2_pass": (_i32, [_vp, C.POINTER(Gatv2Desc)]),
     "dgll_hip_sparse_attn_pass": (_i32, [_vp, C.POINTER(AttnDesc)]),
     "dgll_hip_typed_spmm_pass": (_i32, [_vp, C.POINTER(TypedDesc)]),

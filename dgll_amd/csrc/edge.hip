@@ -756,7 +756,7 @@ static int gat_common(EdgeArgs& a, const int64_t* rowptr, const int32_t* col, in
     return DGLL_OK;
 }
 
-// In-kernel attention dropout (the *_dropout entry points): p in [0, 1) and the device pointer to the two seed words.
+// In-kernel attention dropout (a descriptor with drop_seed): p in [0, 1) and the device pointer to the two seed words.
 static int gat_drop_args(EdgeArgs& a, double p, const uint32_t* seed) {
     if (!(p >= 0.0 && p < 1.0)) {
         set_error("attention dropout: p must lie in [0, 1)");
@@ -869,163 +869,125 @@ static bool rowscore_addressable(int64_t n_cols, int64_t ldh, int dtype) {
     return n_cols > 0 && n_cols <= (1 << 24) && row_bytes < (1 << 24) && n_cols * row_bytes <= (int64_t)0xffffffffll;
 }
 
-static int gat_fwd_impl(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                        const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* edge_scale, void* out,
-                        int64_t ldo, int dtype, float* rowsum, float* rowmax, int64_t n_rows, int heads, int fo,
-                        float alpha, int apply_elu, int mode, void* workspace, size_t workspace_bytes, int raw, int accumulate,
-                        const float* attn2 = nullptr, bool drop = false, double drop_p = 0.0, const uint32_t* drop_seed = nullptr) {
-    if (n_rows <= 0) return DGLL_OK;
-    EdgeArgs a{};
-    int rc = gat_common(a, rowptr, col, n_rows, heads, fo, dtype, alpha, mode, apply_elu);
-    if (rc != DGLL_OK) return rc;
-    DGLL_REQUIRE(H && S && (T || attn2) && out && rowsum, "NULL argument");
-    DGLL_REQUIRE(!attn2 || (!T && mode == 0 && !edge_scale), "the row-score form takes a2 INSTEAD of T (sparseGatConv's form, no attention dropout)");
-    a.attn2 = attn2;
-    if (drop) {
-        DGLL_REQUIRE(mode == 0 && !edge_scale && !raw && !accumulate, "in-kernel dropout: sparseGatConv's form, one launch over the rows");
-        rc = gat_drop_args(a, drop_p, drop_seed);
-        if (rc != DGLL_OK) return rc;
+// Forward and rows pass: how the t_j reach the kernel -- col_score every col_score_stride floats, or attn2 with a NULL col_score (the
+// row-score form: formed from the gathered rows) -- checked, then written to `a` with the other gathered-side inputs.
+static int gat_gathered_side(EdgeArgs& a, const dgll_gat_desc& d) {
+    const bool rowscore = d.attn2 && !d.col_score;
+    if (d.drop_seed) {
+        DGLL_REQUIRE((d.col_score != nullptr) != (d.attn2 != nullptr), "give col_score (with col_score_stride) or attn2, not both");
+        DGLL_REQUIRE(d.n_cols > 0 && d.n_cols < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
     }
-    DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs a rowmax output");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4;
-    DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && ldh >= a.feat && ldo >= a.feat, "H/out must be 16-byte aligned");
-    a.H = H; a.ldh = ldh; a.S = S; a.T = T; a.tstride = t_stride > 0 ? t_stride : heads; a.edge_scale = edge_scale; a.Y = out; a.ldy = ldo;
-    a.out_a = rowsum; a.out_b = mode == 1 ? rowmax : nullptr;
-    DGLL_REQUIRE(mode == 0 || (!raw && !accumulate), "split (raw / accumulate) launches support mode 0 only");
-    a.raw = raw; a.accumulate = accumulate;
-    return gat_run(stream, kGatForward, a, dtype, plan, workspace, workspace_bytes);
-}
-
-DGLL_API int dgll_hip_gat_fwd(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                              const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale, void* out,
-                              int64_t ldo, int dtype, float* rowsum, float* rowmax, int64_t n_rows, int heads, int fo,
-                              float alpha, int apply_elu, int mode, void* workspace, size_t workspace_bytes) {
-    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, T, 0, edge_scale, out, ldo, dtype, rowsum, rowmax, n_rows, heads, fo,
-                        alpha, apply_elu, mode, workspace, workspace_bytes, 0, 0);
-}
-
-DGLL_API int dgll_hip_gat_fwd_ex(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                 const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale, void* out,
-                                 int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int heads, int fo, float alpha,
-                                 int apply_elu, void* workspace, size_t workspace_bytes, int raw, int accumulate) {
-    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, T, 0, edge_scale, out, ldo, dtype, rowsum, nullptr, n_rows, heads, fo,
-                        alpha, apply_elu, 0, workspace, workspace_bytes, raw, accumulate);
-}
-
-DGLL_API int dgll_hip_gat_fwd_strided(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                      const void* H, int64_t ldh, const float* S, const float* T, int t_stride, void* out,
-                                      int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int heads, int fo, float alpha,
-                                      int apply_elu, void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(t_stride >= heads, "t_stride must be at least heads");
-    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, T, t_stride, nullptr, out, ldo, dtype, rowsum, nullptr, n_rows, heads,
-                        fo, alpha, apply_elu, 0, workspace, workspace_bytes, 0, 0);
-}
-
-DGLL_API int dgll_hip_gat_fwd_rowscore(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                       const void* H, int64_t ldh, const float* S, const float* attn2, void* out, int64_t ldo, int dtype,
-                                       float* rowsum, int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu,
-                                       void* workspace, size_t workspace_bytes, int raw, int accumulate) {
-    DGLL_REQUIRE(attn2, "attn2 (a2 of every head, laid out like a row of H) is required");
-    if (!rowscore_addressable(n_cols, ldh, dtype)) {
-        set_error("dgll_hip_gat_fwd_rowscore: H must have at most 2^24 rows and 4 GB (use dgll_hip_gat_fwd_strided)");
+    DGLL_REQUIRE(rowscore || d.col_score_stride == 0 || d.col_score_stride >= d.heads, "col_score_stride must be at least heads");
+    if (rowscore && !rowscore_addressable(d.n_cols, d.ld_h, d.dtype)) {
+        set_error("the row-score form needs h of at most 2^24 rows and 4 GB (fill col_score instead of attn2)");
         return DGLL_ERR_UNSUPPORTED;
     }
-    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, nullptr, 0, nullptr, out, ldo, dtype, rowsum, nullptr, n_rows, heads, fo,
-                        alpha, apply_elu, 0, workspace, workspace_bytes, raw, accumulate, attn2);
+    a.H = d.h; a.ldh = d.ld_h; a.S = d.row_score; a.T = d.col_score; a.attn2 = d.attn2; a.edge_scale = d.edge_scale;
+    a.tstride = !rowscore && d.col_score_stride > 0 ? d.col_score_stride : d.heads;
+    return DGLL_OK;
 }
 
-// Pass 1 of the backward (rows of A or of one column-half of A): DN, DD and grad_S.  accumulate: the C ABI's value of a GatRowsPhase
-// (edge_args.hpp).
-static int gat_bwd_rows_impl(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                             const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* edge_scale,
-                             const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                             const float* rowsum, const float* rowmax, void* dn, int64_t ldn, float* dd, float* sd_out,
-                             int sd_stride, float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu,
-                             int mode, int accumulate, void* workspace, size_t workspace_bytes, float* part3 = nullptr,
-                             const float* attn2 = nullptr, bool drop = false, double drop_p = 0.0, const uint32_t* drop_seed = nullptr) {
-    if (n_rows <= 0) return DGLL_OK;
+static int gat_fwd_impl(void* stream, const dgll_gat_desc& d) {
+    if (d.n_rows <= 0) return DGLL_OK;
     EdgeArgs a{};
-    int rc = gat_common(a, rowptr, col, n_rows, heads, fo, dtype, alpha, mode, apply_elu);
+    int rc = gat_common(a, d.rowptr, d.col, d.n_rows, d.heads, d.fo, d.dtype, d.alpha, d.mode, d.apply_elu);
     if (rc != DGLL_OK) return rc;
-    DGLL_REQUIRE(H && S && (T || attn2) && out && grad_out && rowsum && dn && (dd || sd_out) && grad_S, "NULL argument");
-    DGLL_REQUIRE(!attn2 || (!T && mode == 0 && !edge_scale && accumulate == 3),
-                 "the row-score form takes a2 INSTEAD of T: sparseGatConv's form, one launch over the rows (exact dd_i)");
-    a.attn2 = attn2;
-    if (drop) {
-        DGLL_REQUIRE(mode == 0 && !edge_scale && accumulate == 3, "in-kernel dropout: sparseGatConv's form, one launch over the rows (exact dd_i)");
-        rc = gat_drop_args(a, drop_p, drop_seed);
+    rc = gat_gathered_side(a, d);
+    if (rc != DGLL_OK) return rc;
+    DGLL_REQUIRE(d.h && d.row_score && (d.col_score || d.attn2) && d.out && d.rowsum, "NULL argument");
+    DGLL_REQUIRE(!d.attn2 || (!d.col_score && d.mode == 0 && !d.edge_scale),
+                 "the row-score form takes attn2 INSTEAD of col_score (sparseGatConv's form, no attention dropout array)");
+    if (d.drop_seed) {
+        DGLL_REQUIRE(d.mode == 0 && !d.edge_scale && !d.raw && !d.accumulate, "in-kernel dropout: sparseGatConv's form, one launch over the rows");
+        rc = gat_drop_args(a, d.drop_p, d.drop_seed);
         if (rc != DGLL_OK) return rc;
     }
-    DGLL_REQUIRE(mode == 0 || rowmax, "mode 1 needs the forward's rowmax");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4;
-    DGLL_REQUIRE(vec_ok(H, ldh, esz) && vec_ok(out, ldo, esz) && vec_ok(grad_out, ldg, esz) && vec_ok(dn, ldn, esz),
-                 "matrices must be 16-byte aligned with padded leading dimensions");
-    a.H = H; a.ldh = ldh; a.S = S; a.T = T; a.tstride = t_stride > 0 ? t_stride : heads; a.M = mode == 1 ? rowmax : nullptr;
-    a.DEN = rowsum; a.edge_scale = edge_scale;
-    a.G = grad_out; a.ldg = ldg; a.O = out; a.ldo = ldo; a.Y = dn; a.ldy = ldn; a.out_a = grad_S; a.out_b = dd;
-    a.sd_out = sd_out; a.sd_stride = sd_stride;
-    return gat_run(stream, kGatRows, a, dtype, plan, workspace, workspace_bytes, gat_rows_phase(accumulate), part3);
+    DGLL_REQUIRE(d.mode == 0 || d.rowmax, "mode 1 needs a rowmax output");
+    const int esz = d.dtype == DGLL_BF16 ? 2 : 4;
+    DGLL_REQUIRE(vec_ok(d.h, d.ld_h, esz) && vec_ok(d.out, d.ld_out, esz) && d.ld_h >= a.feat && d.ld_out >= a.feat,
+                 "h / out must be 16-byte aligned with padded pitches");
+    a.Y = d.out; a.ldy = d.ld_out; a.out_a = d.rowsum; a.out_b = d.mode == 1 ? d.rowmax : nullptr;
+    DGLL_REQUIRE(d.mode == 0 || (!d.raw && !d.accumulate), "split (raw / accumulate) launches support mode 0 only");
+    a.raw = d.raw; a.accumulate = d.accumulate;
+    return gat_run(stream, kGatForward, a, d.dtype, d.plan, d.workspace, d.workspace_bytes);
 }
 
-DGLL_API int dgll_hip_gat_bwd_rows(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                   const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                                   const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                                   const float* rowsum, const float* rowmax, void* dn, int64_t ldn, float* dd, float* grad_S,
-                                   int64_t n_rows, int heads, int fo, float alpha, int apply_elu, int mode, int accumulate,
-                                   void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(dd, "NULL dd");
-    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, T, 0, edge_scale, out, ldo, grad_out, ldg, dtype, rowsum, rowmax,
-                             dn, ldn, dd, nullptr, 0, grad_S, n_rows, heads, fo, alpha, apply_elu, mode, accumulate, workspace,
-                             workspace_bytes);
-}
-
-// dgll_hip_gat_bwd_rows for a rows pass SPLIT over column halves of A (the partitioned path: owned-columns CSR, then halo-columns
-// CSR) with the exact dd_i: phase 4 = first launch (writes DN; partial sums -> partial3), 5 = a middle launch, 6 = the last
-// (adds partial3, writes dd and grad_S).  partial3: caller-owned fp32 [n_rows, 3 * heads], the same buffer for every phase.
-DGLL_API int dgll_hip_gat_bwd_rows_split(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                         const void* H, int64_t ldh, const float* S, const float* T, const void* out, int64_t ldo,
-                                         const void* grad_out, int64_t ldg, int dtype, const float* rowsum, void* dn, int64_t ldn,
-                                         float* dd, float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu,
-                                         int phase, float* partial3, void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(dd && partial3 && phase >= 4 && phase <= 6, "dgll_hip_gat_bwd_rows_split: phase 4 (first) / 5 (middle) / 6 (last), non-NULL dd and partial3");
-    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, T, 0, nullptr, out, ldo, grad_out, ldg, dtype, rowsum, nullptr,
-                             dn, ldn, dd, nullptr, 0, grad_S, n_rows, heads, fo, alpha, apply_elu, 0, phase, workspace,
-                             workspace_bytes, partial3);
+// Pass 1 of the backward (rows of A or of one column-half of A): DN, DD and grad_S.
+static int gat_bwd_rows_impl(void* stream, const dgll_gat_desc& d) {
+    if (d.n_rows <= 0) return DGLL_OK;
+    EdgeArgs a{};
+    int rc = gat_common(a, d.rowptr, d.col, d.n_rows, d.heads, d.fo, d.dtype, d.alpha, d.mode, d.apply_elu);
+    if (rc != DGLL_OK) return rc;
+    rc = gat_gathered_side(a, d);
+    if (rc != DGLL_OK) return rc;
+    const GatRowsPhase phase = gat_rows_phase(d.phase);
+    DGLL_REQUIRE(d.dd || d.sd, "NULL dd: the rows pass writes dd_i into dd, into sd, or both");
+    DGLL_REQUIRE(!d.sd || d.sd_stride >= 2 * d.heads, "sd_stride must be at least 2 * heads");
+    DGLL_REQUIRE(phase < kGatRowsExactFirst || (d.dd && d.partial3),
+                 "a split exact rows pass (phase 4 first / 5 middle / 6 last) needs non-NULL dd and partial3");
+    DGLL_REQUIRE(d.h && d.row_score && (d.col_score || d.attn2) && d.out && d.grad_out && d.rowsum && d.dn && d.grad_score, "NULL argument");
+    DGLL_REQUIRE(!d.attn2 || (!d.col_score && d.mode == 0 && !d.edge_scale && phase == kGatRowsExactOnly),
+                 "the row-score form takes attn2 INSTEAD of col_score: sparseGatConv's form, one launch over the rows (exact dd_i)");
+    if (d.drop_seed) {
+        DGLL_REQUIRE(d.mode == 0 && !d.edge_scale && phase == kGatRowsExactOnly,
+                     "in-kernel dropout: sparseGatConv's form, one launch over the rows (exact dd_i)");
+        rc = gat_drop_args(a, d.drop_p, d.drop_seed);
+        if (rc != DGLL_OK) return rc;
+    }
+    DGLL_REQUIRE(d.mode == 0 || d.rowmax, "mode 1 needs the forward's rowmax");
+    const int esz = d.dtype == DGLL_BF16 ? 2 : 4;
+    DGLL_REQUIRE(vec_ok(d.h, d.ld_h, esz) && vec_ok(d.out, d.ld_out, esz) && vec_ok(d.grad_out, d.ld_grad_out, esz) && vec_ok(d.dn, d.ld_dn, esz),
+                 "matrices must be 16-byte aligned with padded pitches");
+    a.M = d.mode == 1 ? d.rowmax : nullptr; a.DEN = d.rowsum;
+    a.G = d.grad_out; a.ldg = d.ld_grad_out; a.O = d.out; a.ldo = d.ld_out; a.Y = d.dn; a.ldy = d.ld_dn; a.out_a = d.grad_score; a.out_b = d.dd;
+    a.sd_out = d.sd; a.sd_stride = d.sd_stride;
+    return gat_run(stream, kGatRows, a, d.dtype, d.plan, d.workspace, d.workspace_bytes, phase, d.partial3);
 }
 
 // Pass 2 of the backward over a transposed structure (rows = source nodes j, columns = destination rows i):
-// grad_H[j] = sum_i w_ij scale_ij DN[i], grad_T[j] = sum_i dz_ij.  Hrow / T_row belong to the rows of this pass, DN / S_col /
-// DD / M_col to its columns (`col_stride` floats per node for S_col and dd_col; 0 = heads).
-static int gat_bwd_cols_impl(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr, const int32_t* t_col,
-                             const int64_t* t_perm, const void* dn, int64_t ldn, const void* Hrow, int64_t ldh,
-                             const float* T_row, const float* S_col, const float* dd_col, int col_stride, const float* rowmax_col,
-                             const float* edge_scale, void* grad_H, int64_t ldgh, float* grad_T, int dtype,
-                             int64_t n_rows_t, int heads, int fo, float alpha, int mode, void* workspace,
-                             size_t workspace_bytes, const float* attn1 = nullptr, const float* attn2 = nullptr,
-                             const float* grad_S_rows = nullptr, bool drop = false, double drop_p = 0.0,
-                             const uint32_t* drop_seed = nullptr) {
-    if (n_rows_t <= 0) return DGLL_OK;
+// grad_H[j] = sum_i w_ij scale_ij DN[i], grad_T[j] = sum_i dz_ij.  h / row_score belong to the rows of this pass, dn / col_score /
+// col_dd / rowmax to its columns.
+static int gat_bwd_cols_impl(void* stream, const dgll_gat_desc& d) {
+    if (d.n_rows <= 0) return DGLL_OK;
     EdgeArgs t{};
-    int rc = gat_common(t, t_rowptr, t_col, n_rows_t, heads, fo, dtype, alpha, mode, 0);
+    int rc = gat_common(t, d.rowptr, d.col, d.n_rows, d.heads, d.fo, d.dtype, d.alpha, d.mode, 0);
     if (rc != DGLL_OK) return rc;
-    DGLL_REQUIRE(dn && Hrow && T_row && S_col && dd_col && grad_H && grad_T, "NULL argument");
-    DGLL_REQUIRE(mode == 0 || rowmax_col, "mode 1 needs the forward's rowmax");
-    DGLL_REQUIRE(!edge_scale || t_perm, "edge_scale needs the transpose permutation");
-    const int esz = dtype == DGLL_BF16 ? 2 : 4;
-    DGLL_REQUIRE(vec_ok(dn, ldn, esz) && vec_ok(Hrow, ldh, esz) && vec_ok(grad_H, ldgh, esz),
-                 "matrices must be 16-byte aligned with padded leading dimensions");
-    t.perm = t_perm; t.H = dn; t.ldh = ldn; t.G = Hrow; t.ldg = ldh; t.S = T_row; t.T = S_col; t.DD = dd_col;
-    t.tstride = col_stride > 0 ? col_stride : heads;
-    DGLL_REQUIRE(!attn1 || (attn2 && grad_S_rows), "the score-gradient epilogue needs a1, a2 and the rows' grad_S");
-    t.attn1 = attn1; t.attn2 = attn2; t.gs_rows = grad_S_rows;
-    if (drop) {
-        DGLL_REQUIRE(mode == 0 && !edge_scale, "in-kernel dropout: sparseGatConv's form");
-        rc = gat_drop_args(t, drop_p, drop_seed);
+    DGLL_REQUIRE(d.col_score_stride == 0 || d.col_score_stride >= d.heads, "col_score_stride must be at least heads");
+    DGLL_REQUIRE(d.dn && d.h && d.row_score && d.col_score && d.col_dd && d.grad_h && d.grad_score, "NULL argument");
+    DGLL_REQUIRE(d.mode == 0 || d.rowmax, "mode 1 needs the forward's rowmax");
+    DGLL_REQUIRE(!d.edge_scale || d.perm, "edge_scale needs the transpose permutation");
+    const int esz = d.dtype == DGLL_BF16 ? 2 : 4;
+    DGLL_REQUIRE(vec_ok(d.dn, d.ld_dn, esz) && vec_ok(d.h, d.ld_h, esz) && vec_ok(d.grad_h, d.ld_grad_h, esz),
+                 "matrices must be 16-byte aligned with padded pitches");
+    t.perm = d.perm; t.H = d.dn; t.ldh = d.ld_dn; t.G = d.h; t.ldg = d.ld_h; t.S = d.row_score; t.T = d.col_score; t.DD = d.col_dd;
+    t.tstride = d.col_score_stride > 0 ? d.col_score_stride : d.heads;
+    DGLL_REQUIRE(!d.attn1 || (d.attn2 && d.grad_s_rows), "the score-gradient epilogue needs attn1, attn2 and the rows' grad_S");
+    t.attn1 = d.attn1; t.attn2 = d.attn2; t.gs_rows = d.grad_s_rows;
+    if (d.drop_seed) {
+        DGLL_REQUIRE(d.mode == 0 && !d.edge_scale, "in-kernel dropout: sparseGatConv's form");
+        rc = gat_drop_args(t, d.drop_p, d.drop_seed);
         if (rc != DGLL_OK) return rc;
     }
-    t.M = mode == 1 ? rowmax_col : nullptr; t.edge_scale = edge_scale; t.Y = grad_H; t.ldy = ldgh; t.out_a = grad_T;
+    t.M = d.mode == 1 ? d.rowmax : nullptr; t.edge_scale = d.edge_scale; t.Y = d.grad_h; t.ldy = d.ld_grad_h; t.out_a = d.grad_score;
     t.out_b = nullptr;
-    return gat_run(stream, kGatTransposed, t, dtype, t_plan, workspace, workspace_bytes);
+    return gat_run(stream, kGatTransposed, t, d.dtype, d.plan, d.workspace, d.workspace_bytes);
+}
+
+static_assert(DGLL_GAT_FORWARD == kGatForward && DGLL_GAT_ROWS == kGatRows && DGLL_GAT_TRANSPOSED == kGatTransposed &&
+              DGLL_GAT_ROWS_STORED_FIRST == kGatRowsStoredFirst && DGLL_GAT_ROWS_STORED_FURTHER == kGatRowsStoredFurther &&
+              DGLL_GAT_ROWS_EXACT_ONLY == kGatRowsExactOnly && DGLL_GAT_ROWS_EXACT_FIRST == kGatRowsExactFirst &&
+              DGLL_GAT_ROWS_EXACT_MIDDLE == kGatRowsExactMiddle && DGLL_GAT_ROWS_EXACT_LAST == kGatRowsExactLast,
+              "the header's pass and phase values are GatPass and GatRowsPhase");
+
+DGLL_API int dgll_hip_gat_pass(void* stream, const dgll_gat_desc* d) {
+    DGLL_REQUIRE(d != nullptr, "NULL descriptor");
+    switch (d->pass) {
+        case DGLL_GAT_FORWARD: return gat_fwd_impl(stream, *d);
+        case DGLL_GAT_ROWS: return gat_bwd_rows_impl(stream, *d);
+        case DGLL_GAT_TRANSPOSED: return gat_bwd_cols_impl(stream, *d);
+    }
+    set_error("pass must be DGLL_GAT_FORWARD, DGLL_GAT_ROWS or DGLL_GAT_TRANSPOSED");
+    return DGLL_ERR_INVALID;
 }
 
 DGLL_API int dgll_hip_debug_gat_choice(int pass, int dtype, int heads, int fo, int mode, int edge_scale, int rowscore, int drop, int phase,
@@ -1044,133 +1006,6 @@ DGLL_API int dgll_hip_debug_gat_choice(int pass, int dtype, int heads, int fo, i
                                     plan ? nnz : 0, plan ? n_chunks : 0, plan ? n_long : 0, y_aligned != 0}, g_gat_tune);
     if (out->error != DGLL_OK) set_error(out->message);
     return out->error;
-}
-
-DGLL_API int dgll_hip_gat_bwd_cols(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr, const int32_t* t_col,
-                                   const int64_t* t_perm, const void* dn, int64_t ldn, const void* Hrow, int64_t ldh,
-                                   const float* T_row, const float* S_col, const float* dd_col, const float* rowmax_col,
-                                   const float* edge_scale, void* grad_H, int64_t ldgh, float* grad_T, int dtype,
-                                   int64_t n_rows_t, int heads, int fo, float alpha, int mode, void* workspace,
-                                   size_t workspace_bytes) {
-    return gat_bwd_cols_impl(stream, t_plan, t_rowptr, t_col, t_perm, dn, ldn, Hrow, ldh, T_row, S_col, dd_col, 0, rowmax_col,
-                             edge_scale, grad_H, ldgh, grad_T, dtype, n_rows_t, heads, fo, alpha, mode, workspace, workspace_bytes);
-}
-
-DGLL_API int dgll_hip_gat_bwd(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,
-                              const int64_t* rowptr, const int32_t* col,          /* A   */
-                              const int64_t* t_rowptr, const int32_t* t_col, const int64_t* t_perm, /* A^T */
-                              const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                              const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                              const float* rowsum, const float* rowmax,
-                              void* dn_scratch, int64_t ldn, float* dd_scratch,
-                              void* grad_H, int64_t ldgh, float* grad_S, float* grad_T,
-                              int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu, int mode,
-                              void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(t_rowptr && t_col, "NULL transposed CSR");
-    int rc = dgll_hip_gat_bwd_rows(stream, plan, rowptr, col, H, ldh, S, T, edge_scale, out, ldo, grad_out, ldg, dtype, rowsum,
-                                   rowmax, dn_scratch, ldn, dd_scratch, grad_S, n_rows, heads, fo, alpha, apply_elu, mode, 3,
-                                   workspace, workspace_bytes);
-    if (rc != DGLL_OK) return rc;
-    // the same scratch is reused: pass 2 is stream-ordered after pass 1
-    return dgll_hip_gat_bwd_cols(stream, t_plan, t_rowptr, t_col, t_perm, dn_scratch, ldn, H, ldh, T, S, dd_scratch, rowmax,
-                                 edge_scale, grad_H, ldgh, grad_T, dtype, n_cols, heads, fo, alpha, mode, workspace,
-                                 workspace_bytes);
-}
-
-// Both backward passes of the sparseGatConv form (mode 0, no attention dropout) with strided score arrays:
-//   T            gathered by the rows pass at T[j * t_stride + head] -- a compact [n_cols, heads] array (t_stride = heads) or
-//                a slot in the padding of the H rows themselves (then the score costs no extra cache line per edge);
-//   sd_scratch   fp32, `sd_stride` floats per destination row: the rows pass leaves {s_i[0:heads], dd_i[0:heads]} side by side
-//                there and the transposed pass gathers both with one line fill -- a separate [n_rows, 2 * heads] buffer
-//                (sd_stride = 2 * heads) or a slot in the padding of the dn_scratch rows.
-DGLL_API int dgll_hip_gat_bwd_rows_strided(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                           const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                                           const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                                           const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch, int sd_stride,
-                                           float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu,
-                                           void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && t_stride >= heads, "bad strided score arguments");
-    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, T, t_stride, nullptr, out, ldo, grad_out, ldg, dtype, rowsum,
-                             nullptr, dn_scratch, ldn, nullptr, sd_scratch, sd_stride, grad_S, n_rows, heads, fo, alpha,
-                             apply_elu, 0, 3, workspace, workspace_bytes);      // the strided form is always the only launch over its rows
-}
-
-DGLL_API int dgll_hip_gat_bwd_rows_rowscore(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                            const void* H, int64_t ldh, const float* S, const float* attn2,
-                                            const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                                            const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch, int sd_stride,
-                                            float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu,
-                                            void* workspace, size_t workspace_bytes) {
-    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && attn2, "bad row-score arguments");
-    if (!rowscore_addressable(n_cols, ldh, dtype)) {
-        set_error("dgll_hip_gat_bwd_rows_rowscore: H must have at most 2^24 rows and 4 GB (use dgll_hip_gat_bwd_rows_strided)");
-        return DGLL_ERR_UNSUPPORTED;
-    }
-    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, nullptr, 0, nullptr, out, ldo, grad_out, ldg, dtype, rowsum,
-                             nullptr, dn_scratch, ldn, nullptr, sd_scratch, sd_stride, grad_S, n_rows, heads, fo, alpha,
-                             apply_elu, 0, 3, workspace, workspace_bytes, nullptr, attn2);
-}
-
-DGLL_API int dgll_hip_gat_bwd_cols_strided(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
-                                           const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
-                                           int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
-                                           void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
-                                           int fo, float alpha, void* workspace, size_t workspace_bytes,
-                                           const float* attn1, const float* attn2, const float* grad_S_rows) {
-    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && T_rows, "bad strided score arguments");
-    return gat_bwd_cols_impl(stream, t_plan, t_rowptr, t_col, nullptr, dn_scratch, ldn, H, ldh, T_rows, sd_scratch,
-                             sd_scratch + heads, sd_stride, nullptr, nullptr, grad_H, ldgh, grad_T, dtype, n_cols, heads, fo,
-                             alpha, 0, workspace, workspace_bytes, attn1, attn2, grad_S_rows);
-}
-
-// ---- the strided / row-score passes with attention dropout drawn in the kernels (gat_dropout.hpp) ---------------------------
-// T (with t_stride) XOR attn2 selects the form of the forward and of the rows pass, as the _strided / _rowscore entry points do.
-DGLL_API int dgll_hip_gat_fwd_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                      const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* attn2,
-                                      void* out, int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int64_t n_cols, int heads,
-                                      int fo, float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
-                                      const uint32_t* seed) {
-    DGLL_REQUIRE((T != nullptr) != (attn2 != nullptr), "give T (with t_stride) or attn2, not both");
-    DGLL_REQUIRE(attn2 || t_stride >= heads, "t_stride must be at least heads");
-    DGLL_REQUIRE(n_cols > 0 && n_cols < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
-    if (attn2 && !rowscore_addressable(n_cols, ldh, dtype)) {
-        set_error("dgll_hip_gat_fwd_dropout: the row-score form needs H of at most 2^24 rows and 4 GB (pass T instead of attn2)");
-        return DGLL_ERR_UNSUPPORTED;
-    }
-    return gat_fwd_impl(stream, plan, rowptr, col, H, ldh, S, T, attn2 ? 0 : t_stride, nullptr, out, ldo, dtype, rowsum, nullptr, n_rows,
-                        heads, fo, alpha, apply_elu, 0, workspace, workspace_bytes, 0, 0, attn2, true, p, seed);
-}
-
-DGLL_API int dgll_hip_gat_bwd_rows_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                           const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                                           const float* attn2, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
-                                           int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
-                                           int sd_stride, float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo,
-                                           float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
-                                           const uint32_t* seed) {
-    DGLL_REQUIRE((T != nullptr) != (attn2 != nullptr), "give T (with t_stride) or attn2, not both");
-    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && (attn2 || t_stride >= heads), "bad strided score arguments");
-    DGLL_REQUIRE(n_cols > 0 && n_cols < ((int64_t)1 << 31), "attention dropout keys on 32-bit node ids");
-    if (attn2 && !rowscore_addressable(n_cols, ldh, dtype)) {
-        set_error("dgll_hip_gat_bwd_rows_dropout: the row-score form needs H of at most 2^24 rows and 4 GB (pass T instead of attn2)");
-        return DGLL_ERR_UNSUPPORTED;
-    }
-    return gat_bwd_rows_impl(stream, plan, rowptr, col, H, ldh, S, T, attn2 ? 0 : t_stride, nullptr, out, ldo, grad_out, ldg, dtype,
-                             rowsum, nullptr, dn_scratch, ldn, nullptr, sd_scratch, sd_stride, grad_S, n_rows, heads, fo, alpha,
-                             apply_elu, 0, 3, workspace, workspace_bytes, nullptr, attn2, true, p, seed);
-}
-
-DGLL_API int dgll_hip_gat_bwd_cols_dropout(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
-                                           const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
-                                           int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
-                                           void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
-                                           int fo, float alpha, void* workspace, size_t workspace_bytes,
-                                           const float* attn1, const float* attn2, const float* grad_S_rows, double p,
-                                           const uint32_t* seed) {
-    DGLL_REQUIRE(sd_scratch && sd_stride >= 2 * heads && T_rows, "bad strided score arguments");
-    return gat_bwd_cols_impl(stream, t_plan, t_rowptr, t_col, nullptr, dn_scratch, ldn, H, ldh, T_rows, sd_scratch,
-                             sd_scratch + heads, sd_stride, nullptr, nullptr, grad_H, ldgh, grad_T, dtype, n_cols, heads, fo,
-                             alpha, 0, workspace, workspace_bytes, attn1, attn2, grad_S_rows, true, p, seed);
 }
 
 // The [nnz, heads] multipliers of a CSR as a tensor, from the one function the passes evaluate (tests; callers that want the mask).
@@ -1221,25 +1056,6 @@ DGLL_API int dgll_host_gat_dropout_mask(const int64_t* rowptr, const int32_t* co
             for (int h = 0; h < heads; ++h)
                 out[k * heads + h] = gat_dropout_multiplier(seed[0], seed[1], (uint32_t)i, (uint32_t)col[k], (uint32_t)h, d);
     return DGLL_OK;
-}
-
-DGLL_API int dgll_hip_gat_bwd_strided(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,
-                                      const int64_t* rowptr, const int32_t* col, const int64_t* t_rowptr, const int32_t* t_col,
-                                      const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                                      const float* T_rows, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
-                                      int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
-                                      int sd_stride, void* grad_H, int64_t ldgh, float* grad_S, float* grad_T, int64_t n_rows,
-                                      int64_t n_cols, int heads, int fo, float alpha, int apply_elu, void* workspace,
-                                      size_t workspace_bytes) {
-    DGLL_REQUIRE(t_rowptr && t_col, "NULL transposed CSR");
-    int rc = dgll_hip_gat_bwd_rows_strided(stream, plan, rowptr, col, H, ldh, S, T, t_stride, out, ldo, grad_out, ldg, dtype,
-                                           rowsum, dn_scratch, ldn, sd_scratch, sd_stride, grad_S, n_rows, heads, fo, alpha,
-                                           apply_elu, workspace, workspace_bytes);
-    if (rc != DGLL_OK) return rc;
-    // the same workspace is reused: pass 2 is stream-ordered after pass 1
-    return dgll_hip_gat_bwd_cols_strided(stream, t_plan, t_rowptr, t_col, dn_scratch, ldn, H, ldh, T_rows, sd_scratch, sd_stride,
-                                         grad_H, ldgh, grad_T, dtype, n_cols, heads, fo, alpha, workspace, workspace_bytes,
-                                         nullptr, nullptr, nullptr);
 }
 
 DGLL_API int dgll_hip_segment_max(void* stream, const int64_t* rowptr, const int32_t* col, const void* X, int64_t ldx,

@@ -154,8 +154,8 @@ __device__ __forceinline__ void for_each_batch(const int32_t* __restrict__ col, 
     }
 }
 
-// Launches of the rows pass (backward over the rows of A, or of one column half of A).  The values are the C ABI's: `accumulate` of
-// dgll_hip_gat_bwd_rows (0, 1, 3 .. 6; anything else reads as 0), `phase` of dgll_hip_gat_bwd_rows_split (4 .. 6).
+// Launches of the rows pass (backward over the rows of A, or of one column half of A).  The values are the C ABI's: `phase` of
+// a DGLL_GAT_ROWS descriptor, DGLL_GAT_ROWS_* of include/dgll_hip.h (anything else reads as 0).
 enum GatRowsPhase {
     kGatRowsStoredFirst = 0,    // dd_i from the stored output row; the first (or only) launch: writes DN, DD, grad_S
     kGatRowsStoredFurther = 1,  // ... a further launch over another column half (grad_S +=)

@@ -11,7 +11,7 @@ Attention dropout of sparseGatConv / SpGAT in training (gatconv.py:132) is drawn
 torch's device generator -- no [nnz, heads] mask tensor; DGLL_GAT_DROPOUT=mask restores the materialised F.dropout mask on the
 first-generation kernels (gatConv / GAT always use that form).
 
-On the GPU each layer is ONE fused kernel (dgll_hip_gat_fwd): edge scores are formed from two per-node dot
+On the GPU each layer is ONE fused kernel (dgll_hip_gat_pass, DGLL_GAT_FORWARD): edge scores are formed from two per-node dot
 products s_i = a[:fo].h_i, t_j = a[fo:].h_j instead of the reference's materialised [2*fo, E] edge_h
 (gatconv.py:122), all heads of SpGAT/GAT run in the same launch (the reference calls heads one by one,
 gatconv.py:168,196), and the backward pass is two more gather passes instead of a dense N x N matmul

@@ -1,5 +1,6 @@
-"""Per-edge operators of the GAT / SpecialSpmm path (C ABI: dgll_hip_sddmm_csr, dgll_hip_gat_fwd/bwd,
+"""Per-edge operators of the GAT / SpecialSpmm path (C ABI: dgll_hip_sddmm_csr, dgll_hip_gat_pass,
 dgll_hip_segment_max).  GPU only; no fallback."""
+import ctypes as C
 import os
 
 import torch
@@ -166,18 +167,37 @@ def gat_dropout_mask(graph, heads, p, seed):
 
 def _rowscore_addressable(h):
     """The row-score kernels address the gathered rows by 32-bit byte offsets formed with a 24-bit multiply: at most 2^24 rows of
-    less than 2^24 bytes, 4 GB in all.  Mirrors rowscore_addressable() of csrc/edge.hip (its entry points refuse what this would let through)."""
+    less than 2^24 bytes, 4 GB in all.  Mirrors rowscore_addressable() of csrc/edge.hip (the passes refuse what this would let through)."""
     row_bytes = h.stride(0) * h.element_size()
     return h.shape[0] <= (1 << 24) and row_bytes < (1 << 24) and h.shape[0] * row_bytes <= 0xFFFFFFFF
 
 
+def _gat_pass(kind, graph, heads, fo, alpha, h, apply_elu=0, mode=0, ws=None, perm=None, n_cols=None, tag=None, **fields):
+    """One dgll_hip_gat_pass launch over `graph` (A; A^T for the transposed pass).  `fields`: further members of dgll_gat_desc by name,
+    as the values the struct takes (addresses, pitches in elements; None is NULL).  ws: (workspace, bytes) shared with another pass,
+    None = this pass's own.  n_cols: None = the graph's."""
+    dev = h.device
+    plan = graph.plan()
+    ws, ws_bytes = _ws(plan, heads, fo, dev) if ws is None else ws
+    # the leading members of the struct in its order (pass .. workspace_bytes), the rest by name: one call fills the descriptor
+    d = _lib.GatDesc(kind, _dtype_code(h), mode, apply_elu, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), _lib.ptr(perm), graph.n_rows,
+                     graph.n_cols if n_cols is None else n_cols, heads, fo, alpha, _lib.ptr(ws), ws_bytes, h=h.data_ptr(), ld_h=h.stride(0),
+                     **fields)
+    _lib.launch("dgll_hip_gat_pass", dev, C.byref(d), tag=tag)
+
+
+def _drop_fields(dropout):
+    """dgll_gat_desc's drop_p / drop_seed of an active (p, seed); nothing without dropout."""
+    return {} if dropout is None else {"drop_p": dropout[0], "drop_seed": dropout[1].data_ptr()}
+
+
 def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_scores, attn2=None, dropout=None):
-    """Forward gather pass on dgll_hip_gat_fwd_strided.  Returns (h with aligned rows, s, t, out, rowsum, packed).
+    """Forward gather pass with strided scores.  Returns (h with aligned rows, s, t, out, rowsum, packed).
     attn2: fp32 [heads * fo], a2 of every head laid out like a row of h (t = h . a2 per head): when the scores cannot ride in the rows'
-    padding the pass forms t_j from the row it gathers anyway instead of fetching T[j] (dgll_hip_gat_fwd_rowscore; the reference builds
-    its logit from the gathered rows too, gatconv.py:122-125).
-    dropout: (p, seed) -- attention dropout drawn in the kernel (dgll_hip_gat_fwd_dropout, either score form; the scores do not ride in
-    the rows' padding then: the in-row form has no dropout instantiation)."""
+    padding the pass forms t_j from the row it gathers anyway instead of fetching T[j] (the row-score form: attn2 with a NULL
+    col_score; the reference builds its logit from the gathered rows too, gatconv.py:122-125).
+    dropout: (p, seed) -- attention dropout drawn in the kernel (either score form; the scores do not ride in the rows' padding then:
+    the in-row form has no dropout instantiation)."""
     _require_cuda(h, s, t, graph.rowptr)
     dev = h.device
     h = _ready(h)
@@ -192,33 +212,27 @@ def _gat_strided_forward(h, s, t, graph, heads, fo, alpha, apply_elu, pack_score
         t_gather = t
     out = _empty_like_rows(graph.n_rows, h)
     rowsum = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
-    plan = graph.plan()
-    ws, ws_bytes = _ws(plan, heads, fo, dev)
     row_scores = attn2 is not None and not packed and ROW_SCORES and _rowscore_addressable(h)
     form = "packed" if packed else ("rowscore" if row_scores else "")
     if dropout is not None:
         form = (form + " dropout").strip()
-    a2 = attn2.detach().to(torch.float32).contiguous() if row_scores else None
-    # (entry, how the t_j reach the pass, the row count that bounds the gathered rows where the entry checks it, what follows ws)
-    if dropout is not None:
-        entry = "dgll_hip_gat_fwd_dropout"
-        scores = (None, 0, a2.data_ptr()) if row_scores else (t_gather.data_ptr(), t_gather.stride(0), None)
-        n_src, extra = (int(h.shape[0]),), (dropout[0], dropout[1].data_ptr())
-    elif row_scores:
-        entry, scores, n_src, extra = "dgll_hip_gat_fwd_rowscore", (a2.data_ptr(),), (int(h.shape[0]),), (0, 0)
+    # how the t_j reach the pass: formed from the gathered rows (attn2, which n_cols = the rows of h bounds), or gathered
+    if row_scores:
+        a2 = attn2.detach().to(torch.float32).contiguous()
+        scores = {"attn2": a2.data_ptr()}
     else:
-        entry, scores, n_src, extra = "dgll_hip_gat_fwd_strided", (t_gather.data_ptr(), t_gather.stride(0)), (), ()
-    _lib.launch(entry, dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), *scores,
-                out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), graph.n_rows, *n_src, heads, fo, float(alpha),
-                int(apply_elu), _lib.ptr(ws), ws_bytes, *extra, tag=lambda: ("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, form))
+        scores = {"col_score": t_gather.data_ptr(), "col_score_stride": t_gather.stride(0)}
+    _gat_pass(_lib.GAT_FORWARD, graph, heads, fo, float(alpha), h, apply_elu=int(apply_elu), n_cols=int(h.shape[0]), row_score=s.data_ptr(),
+              out=out.data_ptr(), ld_out=out.stride(0), rowsum=rowsum.data_ptr(), **scores, **_drop_fields(dropout),
+              tag=lambda: ("gat", "fwd", heads, fo, str(h.dtype), graph.nnz, form))
     return h, s, t, out, rowsum, packed
 
 
 def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, apply_elu, packed, attn=None, rows_first=False,
                           dropout=None):
-    """Both backward gather passes (dgll_hip_gat_bwd_rows_strided, _cols_strided).  attn = (a1, a2) fp32 [heads * fo]: the
+    """Both backward gather passes (rows of A, then rows of A^T) with strided scores.  attn = (a1, a2) fp32 [heads * fo]: the
     scores are S = H.a1, T = H.a2 per head and their contribution to grad_h is added by the second pass's epilogue.
-    dropout: the forward's (p, seed): both passes draw the same mask again (dgll_hip_gat_bwd_rows_dropout, _cols_dropout).
+    dropout: the forward's (p, seed): both passes draw the same mask again.
     Returns (grad_h, grad_s, grad_t)."""
     dev, esz, width = h.device, h.element_size(), heads * fo
     g = _ready(g.to(h.dtype))
@@ -232,10 +246,8 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
     grad_h = _empty_like_rows(graph.n_cols, h)
     grad_s = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
     grad_t = torch.empty((graph.n_cols, heads), dtype=torch.float32, device=dev)
-    plan, t_plan = graph.plan(), gt.plan()
-    ws, ws_bytes = _ws(plan, heads, fo, dev, t_plan)
+    ws = _ws(graph.plan(), heads, fo, dev, gt.plan())      # one workspace: the transposed pass is stream-ordered after the rows pass
     kind = (heads, fo, str(h.dtype), graph.nnz, "packed" if packed else ("dropout" if dropout is not None else ""))
-    wsp = _lib.ptr(ws)
     a1 = a2 = None
     gs_cols = grad_s
     if attn is not None:
@@ -247,32 +259,30 @@ def _gat_strided_backward(g, h, s, t, out, rowsum, graph, heads, fo, alpha, appl
             gs_cols = torch.zeros((graph.n_cols, heads), dtype=torch.float32, device=dev)
         a1, a2 = (v.detach().to(torch.float32).contiguous() for v in attn)
     rows_rowscore = a2 is not None and not packed and ROW_SCORES_BWD and _rowscore_addressable(h)
-    # (entry, how the t_j reach the pass, the row count that bounds the gathered rows where the entry checks it, what follows ws)
-    if dropout is not None:
-        entry = "dgll_hip_gat_bwd_rows_dropout"
-        scores = (None, 0, a2.data_ptr()) if rows_rowscore else (t_gather.data_ptr(), t_gather.stride(0), None)
-        n_src, extra = (int(h.shape[0]),), (dropout[0], dropout[1].data_ptr())
-    elif rows_rowscore:      # t_j from the gathered rows, as in the forward
-        entry, scores, n_src, extra = "dgll_hip_gat_bwd_rows_rowscore", (a2.data_ptr(),), (int(h.shape[0]),), ()
+    if rows_rowscore:      # t_j from the gathered rows, as in the forward
+        scores = {"attn2": a2.data_ptr()}
     else:
-        entry, scores, n_src, extra = "dgll_hip_gat_bwd_rows_strided", (t_gather.data_ptr(), t_gather.stride(0)), (), ()
-    _lib.launch(entry, dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), *scores,
-                out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h), rowsum.data_ptr(), dn.data_ptr(), dn.stride(0),
-                sd.data_ptr(), sd.stride(0), grad_s.data_ptr(), graph.n_rows, *n_src, heads, fo, alpha, apply_elu, wsp, ws_bytes, *extra,
-                tag=lambda: ("gat", "bwd_rows") + (kind[:4] + (("rowscore " + kind[4]).strip(),) if rows_rowscore else kind))
+        scores = {"col_score": t_gather.data_ptr(), "col_score_stride": t_gather.stride(0)}
+    drop = _drop_fields(dropout)
+    # the strided form is always the only launch over its rows: the exact dd_i
+    _gat_pass(_lib.GAT_ROWS, graph, heads, fo, alpha, h, apply_elu=apply_elu, ws=ws, phase=_lib.GAT_ROWS_EXACT_ONLY, n_cols=int(h.shape[0]),
+              row_score=s.data_ptr(), out=out.data_ptr(), ld_out=out.stride(0), grad_out=g.data_ptr(), ld_grad_out=g.stride(0),
+              rowsum=rowsum.data_ptr(), dn=dn.data_ptr(), ld_dn=dn.stride(0), sd=sd.data_ptr(), sd_stride=sd.stride(0),
+              grad_score=grad_s.data_ptr(), **scores, **drop,
+              tag=lambda: ("gat", "bwd_rows") + (kind[:4] + (("rowscore " + kind[4]).strip(),) if rows_rowscore else kind))
     if gs_cols is not grad_s:
         gs_cols[:graph.n_rows].copy_(grad_s)
-    _lib.launch("dgll_hip_gat_bwd_cols_strided" if dropout is None else "dgll_hip_gat_bwd_cols_dropout", dev,
-                t_plan, gt.rowptr.data_ptr(), gt.col.data_ptr(), dn.data_ptr(), dn.stride(0), h.data_ptr(), h.stride(0),
-                t.data_ptr(), sd.data_ptr(), sd.stride(0), grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(h),
-                graph.n_cols, heads, fo, alpha, wsp, ws_bytes, _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(gs_cols if a1 is not None else None),
-                *(() if dropout is None else (dropout[0], dropout[1].data_ptr())), tag=lambda: ("gat", "bwd_cols") + kind)
+    # the rows pass left {s_i, dd_i} side by side in sd: the columns' scores and, `heads` floats behind them, their dd
+    _gat_pass(_lib.GAT_TRANSPOSED, gt, heads, fo, alpha, h, ws=ws, dn=dn.data_ptr(), ld_dn=dn.stride(0), row_score=t.data_ptr(),
+              col_score=sd.data_ptr(), col_dd=sd.data_ptr() + 4 * heads, col_score_stride=sd.stride(0), grad_h=grad_h.data_ptr(),
+              ld_grad_h=grad_h.stride(0), grad_score=grad_t.data_ptr(), attn1=_lib.ptr(a1), attn2=_lib.ptr(a2),
+              grad_s_rows=_lib.ptr(gs_cols if a1 is not None else None), **drop, tag=lambda: ("gat", "bwd_cols") + kind)
     return grad_h, grad_s, grad_t
 
 
 class _GatAggregateStrided(torch.autograd.Function):
     """sparseGatConv's form (exp(-leakyrelu); attention dropout drawn in the kernels from (dropout_p, dropout_seed) when given) on
-    the second-generation kernels (dgll_hip_gat_fwd_strided / _bwd_*_strided, or their *_dropout forms).  These passes are bound by cache-line fills per edge, so per-node scalars
+    the second-generation kernels.  These passes are bound by cache-line fills per edge, so per-node scalars
     that are gathered per edge live next to what is gathered anyway: with `pack_scores` (the caller owns the padding behind
     h's rows) T sits in the padding of the feature rows -- a 47-class output row is 96 of 128 bytes -- and the backward keeps
     {s_i, dd_i} in the padding of its DN rows; without room they are compact / side-by-side arrays."""
@@ -359,11 +369,9 @@ class _GatAggregate(torch.autograd.Function):
         rowmax = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev) if mode == 1 else None
         if edge_scale is not None:
             edge_scale = edge_scale.to(torch.float32).contiguous()
-        plan = graph.plan()
-        ws, ws_bytes = _ws(plan, heads, fo, dev)
-        _lib.launch("dgll_hip_gat_fwd", dev, plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(),
-                    t.data_ptr(), _lib.ptr(edge_scale), out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(), _lib.ptr(rowmax),
-                    graph.n_rows, heads, fo, float(alpha), int(apply_elu), int(mode), _lib.ptr(ws), ws_bytes)
+        _gat_pass(_lib.GAT_FORWARD, graph, heads, fo, float(alpha), h, apply_elu=int(apply_elu), mode=int(mode), row_score=s.data_ptr(),
+                  col_score=t.data_ptr(), edge_scale=_lib.ptr(edge_scale), out=out.data_ptr(), ld_out=out.stride(0), rowsum=rowsum.data_ptr(),
+                  rowmax=_lib.ptr(rowmax))
         ctx.graph, ctx.cfg = graph, (heads, fo, float(alpha), int(apply_elu), int(mode))
         ctx.save_for_backward(h, s, t, edge_scale, out, rowsum, rowmax)
         return out
@@ -381,13 +389,14 @@ class _GatAggregate(torch.autograd.Function):
         grad_h = _empty_padded(graph.n_cols, heads * fo, h.dtype, dev)
         grad_s = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=dev)
         grad_t = torch.empty((graph.n_cols, heads), dtype=torch.float32, device=dev)
-        plan, t_plan = graph.plan(), gt.plan()
-        ws, ws_bytes = _ws(plan, heads, fo, dev, t_plan)
-        _lib.launch("dgll_hip_gat_bwd", dev, plan, t_plan, graph.rowptr.data_ptr(), graph.col.data_ptr(), gt.rowptr.data_ptr(),
-                    gt.col.data_ptr(), perm.data_ptr(), h.data_ptr(), h.stride(0), s.data_ptr(), t.data_ptr(), _lib.ptr(edge_scale),
-                    out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(h), rowsum.data_ptr(), _lib.ptr(rowmax),
-                    dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_h.data_ptr(), grad_h.stride(0), grad_s.data_ptr(),
-                    grad_t.data_ptr(), graph.n_rows, graph.n_cols, heads, fo, alpha, apply_elu, mode, _lib.ptr(ws), ws_bytes)
+        ws = _ws(graph.plan(), heads, fo, dev, gt.plan())      # one workspace: the transposed pass is stream-ordered after the rows pass
+        _gat_pass(_lib.GAT_ROWS, graph, heads, fo, alpha, h, apply_elu=apply_elu, mode=mode, ws=ws, phase=_lib.GAT_ROWS_EXACT_ONLY,
+                  row_score=s.data_ptr(), col_score=t.data_ptr(), edge_scale=_lib.ptr(edge_scale), out=out.data_ptr(), ld_out=out.stride(0),
+                  grad_out=g.data_ptr(), ld_grad_out=g.stride(0), rowsum=rowsum.data_ptr(), rowmax=_lib.ptr(rowmax), dn=dn.data_ptr(),
+                  ld_dn=dn.stride(0), dd=dd.data_ptr(), grad_score=grad_s.data_ptr())
+        _gat_pass(_lib.GAT_TRANSPOSED, gt, heads, fo, alpha, h, mode=mode, ws=ws, perm=perm, dn=dn.data_ptr(), ld_dn=dn.stride(0),
+                  row_score=t.data_ptr(), col_score=s.data_ptr(), col_dd=dd.data_ptr(), rowmax=_lib.ptr(rowmax), edge_scale=_lib.ptr(edge_scale),
+                  grad_h=grad_h.data_ptr(), ld_grad_h=grad_h.stride(0), grad_score=grad_t.data_ptr())
         return grad_h, grad_s, grad_t, None, None, None, None, None, None, None
 
 
@@ -430,11 +439,9 @@ def gat_layer(graph, h, A, heads, alpha, apply_elu=True, pack_scores=False, drop
 def gat_fwd_part(graph, h, s_rows, t_cols, out, rowsum, heads, fo, alpha, apply_elu, raw, accumulate):
     """One half of a split forward: rows of `graph` gather from `h` / `t_cols`; numerator into `out`, denominator into
     `rowsum` (raw), optionally on top of what a previous launch left there (accumulate)."""
-    dev = h.device
-    ws, nbytes = _ws(graph.plan(), heads, fo, dev)
-    _lib.launch("dgll_hip_gat_fwd_ex", dev, graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h.data_ptr(), h.stride(0),
-                s_rows.data_ptr(), t_cols.data_ptr(), None, out.data_ptr(), out.stride(0), _dtype_code(h), rowsum.data_ptr(),
-                graph.n_rows, heads, fo, float(alpha), int(apply_elu), _lib.ptr(ws), nbytes, int(raw), int(accumulate))
+    _gat_pass(_lib.GAT_FORWARD, graph, heads, fo, float(alpha), h, apply_elu=int(apply_elu), row_score=s_rows.data_ptr(),
+              col_score=t_cols.data_ptr(), out=out.data_ptr(), ld_out=out.stride(0), rowsum=rowsum.data_ptr(), raw=int(raw),
+              accumulate=int(accumulate))
 
 
 def gat_bwd_rows_part(graph, h_cols, s_rows, t_cols, out, g, rowsum, dn, dd, grad_s, heads, fo, alpha, apply_elu, accumulate,
@@ -442,29 +449,20 @@ def gat_bwd_rows_part(graph, h_cols, s_rows, t_cols, out, g, rowsum, dn, dd, gra
     """Rows pass over one column half of A.  accumulate: False / 0 = first (or only) launch (writes DN, dd, grad_s; dd_i from the
     stored output row), True / 1 = a further half (grad_s +=), 3 = DECLARED the only launch over these rows: exact dd_i;
     4 / 5 / 6 with `partial` (fp32 [n_rows, 3 * heads], the same buffer every time) = first / middle / last launch of a SPLIT
-    exact pass (dgll_hip_gat_bwd_rows_split)."""
-    dev = out.device
-    ws, nbytes = _ws(graph.plan(), heads, fo, dev)
-    head = (graph.plan(), graph.rowptr.data_ptr(), graph.col.data_ptr(), h_cols.data_ptr(), h_cols.stride(0), s_rows.data_ptr(),
-            t_cols.data_ptr())
-    if int(accumulate) >= 4:
-        if partial is None or partial.dtype != torch.float32 or partial.numel() < graph.n_rows * 3 * heads or not partial.is_contiguous():
-            raise ValueError("a split exact rows pass needs a contiguous fp32 [n_rows, 3 * heads] `partial` buffer")
-        _lib.launch("dgll_hip_gat_bwd_rows_split", dev, *head, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(out),
-                    rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(), graph.n_rows, heads, fo,
-                    float(alpha), int(apply_elu), int(accumulate), partial.data_ptr(), _lib.ptr(ws), nbytes)
-        return
-    _lib.launch("dgll_hip_gat_bwd_rows", dev, *head, None, out.data_ptr(), out.stride(0), g.data_ptr(), g.stride(0), _dtype_code(out),
-                rowsum.data_ptr(), None, dn.data_ptr(), dn.stride(0), dd.data_ptr(), grad_s.data_ptr(), graph.n_rows, heads, fo,
-                float(alpha), int(apply_elu), 0, int(accumulate), _lib.ptr(ws), nbytes)
+    exact pass (DGLL_GAT_ROWS_EXACT_FIRST / _MIDDLE / _LAST).  The values are the descriptor's `phase`."""
+    split = int(accumulate) >= _lib.GAT_ROWS_EXACT_FIRST
+    if split and (partial is None or partial.dtype != torch.float32 or partial.numel() < graph.n_rows * 3 * heads
+                  or not partial.is_contiguous()):
+        raise ValueError("a split exact rows pass needs a contiguous fp32 [n_rows, 3 * heads] `partial` buffer")
+    _gat_pass(_lib.GAT_ROWS, graph, heads, fo, float(alpha), h_cols, apply_elu=int(apply_elu), phase=int(accumulate),
+              row_score=s_rows.data_ptr(), col_score=t_cols.data_ptr(), out=out.data_ptr(), ld_out=out.stride(0), grad_out=g.data_ptr(),
+              ld_grad_out=g.stride(0), rowsum=rowsum.data_ptr(), dn=dn.data_ptr(), ld_dn=dn.stride(0), dd=dd.data_ptr(),
+              grad_score=grad_s.data_ptr(), partial3=partial.data_ptr() if split else None)
 
 
 def gat_bwd_cols_part(graph_t, dn, h_rows, t_rows, s_cols, dd_cols, grad_h, grad_t, heads, fo, alpha):
     """Pass 2 over a transposed structure `graph_t` (rows = source nodes with features h_rows / scores t_rows, columns =
     destination rows with dn / s_cols / dd_cols)."""
-    dev = dn.device
-    ws, nbytes = _ws(graph_t.plan(), heads, fo, dev)
-    _lib.launch("dgll_hip_gat_bwd_cols", dev, graph_t.plan(), graph_t.rowptr.data_ptr(), graph_t.col.data_ptr(), None, dn.data_ptr(),
-                dn.stride(0), h_rows.data_ptr(), h_rows.stride(0), t_rows.data_ptr(), s_cols.data_ptr(), dd_cols.data_ptr(), None, None,
-                grad_h.data_ptr(), grad_h.stride(0), grad_t.data_ptr(), _dtype_code(dn), graph_t.n_rows, heads, fo, float(alpha), 0,
-                _lib.ptr(ws), nbytes)
+    _gat_pass(_lib.GAT_TRANSPOSED, graph_t, heads, fo, float(alpha), h_rows, dn=dn.data_ptr(), ld_dn=dn.stride(0), row_score=t_rows.data_ptr(),
+              col_score=s_cols.data_ptr(), col_dd=dd_cols.data_ptr(), grad_h=grad_h.data_ptr(), ld_grad_h=grad_h.stride(0),
+              grad_score=grad_t.data_ptr())

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DGLL_HIP_ABI_VERSION 1
+#define DGLL_HIP_ABI_VERSION 2
 
 enum { DGLL_OK = 0, DGLL_ERR_INVALID = -1, DGLL_ERR_HIP = -2, DGLL_ERR_UNSUPPORTED = -3, DGLL_ERR_WORKSPACE = -4 };
 enum { DGLL_F32 = 0, DGLL_BF16 = 1 };
@@ -171,173 +171,98 @@ int dgll_hip_sddmm_csr(void* stream, const int64_t* rowptr, const int32_t* col,
                        const void* G, int64_t ldg, const void* B, int64_t ldb, int dtype,
                        float* edge_out, int64_t n_rows, int feat);
 
-/* ---- a6 / a8 / a9: fused multi-head edge-softmax + aggregation ------------------------------------------
- * All `heads` attention heads of one layer in one launch (the reference loops heads in Python,
- * gatconv.py:168,196).  H is [n_cols, heads*fo] (the concatenated per-head X.W of gatconv.py:117), S and T are
- * fp32 [n, heads] with S[i,k] = a_k[:fo].h_i^k, T[j,k] = a_k[fo:].h_j^k (gatconv.py:122-125 without
- * materialising edge_h).  mode 0 = sparseGatConv: w_ij = exp(-leakyrelu_alpha(S_i+T_j)) (gatconv.py:125);
- * mode 1 = gatConv restricted to the adjacency's nonzeros: softmax_j(+leakyrelu) with the row maximum
- * subtracted (gatconv.py:34-36,53-54).  out_i = act(sum_j w_ij*scale_ij*h_j / sum_j w_ij), act = ELU when
- * apply_elu (gatconv.py:143-145); `edge_scale` (fp32 [nnz, heads] or NULL) carries attention-dropout
- * multipliers, applied after the row sum exactly as gatconv.py:129-135 orders them.  rowsum (and rowmax in
- * mode 1) are fp32 [n_rows, heads] outputs kept for the backward pass.  `fo` must make fo*sizeof(dtype)/16 a
- * power of two (the host pads each head with zero columns).                                                */
-int dgll_hip_gat_fwd(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                     const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                     void* out, int64_t ldo, int dtype, float* rowsum, float* rowmax,
-                     int64_t n_rows, int heads, int fo, float alpha, int apply_elu, int mode,
-                     void* workspace, size_t workspace_bytes);
-/* Scratch for the long-row partials of dgll_hip_gat_fwd / _bwd with this plan (0 without long rows). `plan` (and
- * `t_plan`, the plan of A^T, in the backward) may be NULL: every row is then handled by one wavefront.          */
+/* ---- a6 / a8 / a9: fused multi-head edge-softmax + aggregation: three gather passes behind one entry point (csrc/edge.hip) ------
+ * All `heads` attention heads of one layer in one launch (the reference loops heads in Python, gatconv.py:168,196), nothing stored
+ * per edge.  Over the rows i of a CSR matrix A [n_rows x n_cols], with per-node scores s_i = a_k[:fo].h_i^k, t_j = a_k[fo:].h_j^k
+ * (gatconv.py:122-125 without materialising edge_h):
+ *     mode 0 (sparseGatConv)  w_ij = exp(-leakyrelu_alpha(s_i + t_j))                                        (gatconv.py:125)
+ *     mode 1 (gatConv on the adjacency's nonzeros)  softmax_j(+leakyrelu), the row maximum subtracted        (gatconv.py:34-36,53-54)
+ *     out_i = act( sum_j w_ij scale_ij h_j / sum_j w_ij ),  act = ELU when apply_elu                         (gatconv.py:143-145)
+ * scale_ij: `edge_scale` (fp32 [nnz, heads] or NULL), applied after the row sum exactly as gatconv.py:129-135 orders it.
+ *   DGLL_GAT_FORWARD     rowptr / col / plan = A.  Reads h [n_cols, heads * fo], row_score = S fp32 [n_rows, heads] and the t_j
+ *                        (below); writes out [n_rows, heads * fo], rowsum and (mode 1) rowmax, fp32 [n_rows, heads], kept for the
+ *                        backward.  Mode 0 only: raw != 0 leaves the row un-normalised (numerator in out, denominator in rowsum);
+ *                        accumulate != 0 adds the numerator / denominator already there, then (unless raw) normalises and applies
+ *                        the ELU -- a row whose neighbours are split over an owned-columns and a halo-columns CSR.
+ *   DGLL_GAT_ROWS        the same A.  Reads h, row_score = S, the t_j, out, grad_out, rowsum, (mode 1) rowmax; writes dn [n_rows,
+ *                        heads * fo], grad_score = grad_S fp32 [n_rows, heads] and dd_i -- into dd (compact fp32 [n_rows, heads])
+ *                        and / or, with sd, as {s_i[0:heads], dd_i[0:heads]} side by side every sd_stride (>= 2 heads) floats, which
+ *                        the transposed pass gathers with ONE line fill: a separate buffer or a slot in the padding of the dn rows.
+ *                        At least one of dd / sd.  `phase`:
+ *                          DGLL_GAT_ROWS_STORED_FIRST    dd_i = -dn_i . hp_i, hp_i recovered from the stored output row; the first (or
+ *                                                        only) launch over these rows;
+ *                          DGLL_GAT_ROWS_STORED_FURTHER  a further launch over another column half (grad_S +=, dn / dd left alone);
+ *                          DGLL_GAT_ROWS_EXACT_ONLY      DECLARED the only launch over these rows (mode 0): dd_i from the pass's own
+ *                                                        dot products, sum_j w_ij (dn_i . h_j) / den_i -- exact in the stored operands;
+ *                          DGLL_GAT_ROWS_EXACT_FIRST / _MIDDLE / _LAST   the exact dd_i over SEVERAL column halves (ds_i is bilinear in
+ *                                                        the sums (sum c.dot, sum c, sum w.dot), so no launch can finalise its own
+ *                                                        share): the first writes dn and parks the sums in partial3, the last adds
+ *                                                        partial3 and writes dd and grad_S.  partial3: fp32 [n_rows, 3 * heads],
+ *                                                        caller-owned, the same buffer for every phase; dd required.
+ *   DGLL_GAT_TRANSPOSED  rowptr / col / plan = A^T (n_rows = the source nodes), perm[k] = A's edge slot of A^T's k-th edge (needed
+ *                        with edge_scale only).  Reads dn (gathered), h (its own rows), row_score = T of its rows, col_score = S and
+ *                        col_dd = dd of its columns (both every col_score_stride floats: col_score = sd, col_dd = sd + heads,
+ *                        col_score_stride = sd_stride after a rows pass that wrote sd), (mode 1) rowmax of its columns; writes grad_h
+ *                        [n_rows, heads * fo] and grad_score = grad_T fp32 [n_rows, heads].  attn1 / attn2 / grad_s_rows (all three
+ *                        or none; attn* fp32 [heads * fo] laid out like a row of h, grad_s_rows = grad_S of this pass's rows): when
+ *                        S = H.a1, T = H.a2 per head, their own share grad_S[j] * attn1 + grad_T[j] * attn2 of grad_h is added in the
+ *                        epilogue instead of by a separate product and add.
+ * The t_j of the forward and the rows pass (the passes are bound by cache-line fills per edge: four for a 512-byte row plus one for
+ * every separate per-node array gathered per edge):
+ *   col_score  read at col_score[j * col_score_stride + head] (0 = heads, else >= heads): a compact [n_cols, heads] array, or a slot
+ *              in the PADDING of the h rows themselves (a 47-class bf16 row is 94 of 128 bytes: col_score = (float*)((char*)h + 96),
+ *              col_score_stride = ld_h * elem_size / 4) -- the in-row form: the score shares the row's cache line and costs nothing;
+ *   attn2      with a NULL col_score (mode 0, no edge_scale; rows pass: DGLL_GAT_ROWS_EXACT_ONLY): t_j = h_j . attn2 per head is FORMED
+ *              from the gathered row, no score is fetched per edge (bf16: attn2 rounded to bf16 for the packed dot product, as the
+ *              caller's score product rounds it).  The gathers use 32-bit byte offsets: h of at most 2^24 rows (n_cols) and 4 GB,
+ *              DGLL_ERR_UNSUPPORTED past that -- fill col_score instead.
+ * Attention dropout drawn in the kernels (gatconv.py:132: the row sum keeps every edge, the aggregation loses a fraction drop_p of
+ * them, survivors scaled by 1 / (1 - drop_p)): drop_seed != NULL, mode 0 without edge_scale, one launch over the rows (no raw /
+ * accumulate, DGLL_GAT_ROWS_EXACT_ONLY), col_score XOR attn2, 32-bit node ids.  drop_p in [0, 1), anything else is
+ * DGLL_ERR_INVALID.  drop_seed is a DEVICE pointer to two 32-bit words, read by the kernels: a captured graph whose seed words are
+ * rewritten between replays draws a fresh mask on every replay; the backward passes must be given the words the forward read.  The
+ * multiplier of edge (row i, column j), head k is a pure function of (seed, i, j, k) that each pass evaluates for the edges it walks
+ * (the transposed pass swaps the ids back; duplicate (i, j) entries share a draw).  There is no in-row form with dropout.
+ * Matrices of `dtype`, pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned bases.  fo (per-head width) is a multiple of the
+ * vector (4 fp32 / 8 bf16 columns); mode 1 and edge_scale need a power of two of them (the host pads each head with zero columns).
+ * plan (NULL: every row is handled by one wavefront) splits long rows, whose partials need `workspace` of
+ * dgll_hip_gat_workspace_bytes() bytes.  An empty pass (n_rows <= 0) is DGLL_OK.  Nothing is launched before every check has passed;
+ * no pass allocates, synchronises or reads anything back: the calls can be captured into a graph.                                  */
+enum { DGLL_GAT_FORWARD = 0, DGLL_GAT_ROWS = 1, DGLL_GAT_TRANSPOSED = 2 };
+enum { DGLL_GAT_ROWS_STORED_FIRST = 0, DGLL_GAT_ROWS_STORED_FURTHER = 1, DGLL_GAT_ROWS_EXACT_ONLY = 3,
+       DGLL_GAT_ROWS_EXACT_FIRST = 4, DGLL_GAT_ROWS_EXACT_MIDDLE = 5, DGLL_GAT_ROWS_EXACT_LAST = 6 };
+typedef struct dgll_gat_desc {
+    int pass; int dtype; int mode; int apply_elu;
+    const dgll_csr_plan* plan; const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols;
+    int heads; int fo; float alpha;
+    void* workspace; size_t workspace_bytes;
+    const float* edge_scale;
+    double drop_p; const uint32_t* drop_seed;
+    const void* h; int64_t ld_h;
+    void* out; int64_t ld_out;
+    const void* grad_out; int64_t ld_grad_out;
+    void* dn; int64_t ld_dn;
+    void* grad_h; int64_t ld_grad_h;
+    const float* row_score;
+    const float* col_score; int col_score_stride; const float* col_dd;
+    const float* attn1; const float* attn2; const float* grad_s_rows;
+    float* rowsum; float* rowmax;
+    float* dd; float* sd; int sd_stride;
+    float* grad_score;
+    float* partial3;
+    int raw; int accumulate; int phase;
+} dgll_gat_desc;
+int dgll_hip_gat_pass(void* stream, const dgll_gat_desc* d);
+/* Scratch for the long-row partials of a pass over this plan's structure (0 without long rows or a plan). */
 size_t dgll_hip_gat_workspace_bytes(const dgll_csr_plan* plan, int heads, int fo);
 
-/* Backward of dgll_hip_gat_fwd: two gather passes (rows of A, then rows of A^T given by t_rowptr/t_col with
- * t_perm[k] = A's edge slot of A^T's k-th edge), nothing stored per edge.  Scratch: dn_scratch
- * [n_rows, ldn] in `dtype`, dd_scratch fp32 [n_rows, heads].  Outputs: grad_H [n_cols, ldgh] in `dtype`,
- * grad_S fp32 [n_rows, heads], grad_T fp32 [n_cols, heads].                                                 */
-int dgll_hip_gat_bwd(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,
-                     const int64_t* rowptr, const int32_t* col,
-                     const int64_t* t_rowptr, const int32_t* t_col, const int64_t* t_perm,
-                     const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                     const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                     const float* rowsum, const float* rowmax,
-                     void* dn_scratch, int64_t ldn, float* dd_scratch,
-                     void* grad_H, int64_t ldgh, float* grad_S, float* grad_T,
-                     int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu, int mode,
-                     void* workspace, size_t workspace_bytes);   /* >= max of the two plans' workspace bytes */
-
-/* The same three launches as separate entry points for the partitioned (multi-GPU) path, where a destination row's
- * neighbours are split over an owned-columns CSR and a halo-columns CSR (mode 0 only):
- *   dgll_hip_gat_fwd_ex   raw != 0: leave the row un-normalised (numerator in `out`, denominator in rowsum);
- *                         accumulate != 0: add the numerator / denominator already there, then (unless raw) normalise + ELU;
- *   dgll_hip_gat_bwd_rows pass 1 over one half; accumulate = 0: first (or only) launch, writes DN / DD / grad_S, dd_i = -DN_i . hp_i with
- *                         hp_i recovered from the stored output row; 1: a further launch over another column half (grad_S +=, DN / DD
- *                         left alone); 3: DECLARED the only launch over these rows (sparseGatConv form): dd_i is formed from the
- *                         pass's own dot products, sum_j w_ij (DN_i . h_j) / den_i -- exact in the stored operands (what
- *                         dgll_hip_gat_bwd and the *_strided entry points do);
- *   dgll_hip_gat_bwd_cols pass 2 over one transposed structure: rows = source nodes (Hrow, T_row), columns = destination
- *                         rows (dn, S_col, dd_col, rowmax_col).                                                     */
-/* dgll_hip_gat_bwd_rows_split: the rows pass over SEVERAL column halves of A with the exact dd_i (ds_i is bilinear in the sums
- * (sum c.dot, sum c, sum w.dot), so no launch can finalise its own share): phase 4 = first launch (writes DN, parks the sums in
- * partial3), 5 = a middle one, 6 = the last (adds partial3, writes dd and grad_S).  partial3: fp32 [n_rows, 3 * heads], caller-owned,
- * the same buffer for every phase; mode 0 (sparseGatConv form) only.                                                           */
-int dgll_hip_gat_bwd_rows_split(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                const void* H, int64_t ldh, const float* S, const float* T, const void* out, int64_t ldo,
-                                const void* grad_out, int64_t ldg, int dtype, const float* rowsum, void* dn, int64_t ldn, float* dd,
-                                float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu, int phase,
-                                float* partial3, void* workspace, size_t workspace_bytes);
-int dgll_hip_gat_fwd_ex(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                        const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                        void* out, int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int heads, int fo, float alpha,
-                        int apply_elu, void* workspace, size_t workspace_bytes, int raw, int accumulate);
-int dgll_hip_gat_bwd_rows(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                          const void* H, int64_t ldh, const float* S, const float* T, const float* edge_scale,
-                          const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                          const float* rowsum, const float* rowmax, void* dn, int64_t ldn, float* dd, float* grad_S,
-                          int64_t n_rows, int heads, int fo, float alpha, int apply_elu, int mode, int accumulate,
-                          void* workspace, size_t workspace_bytes);
-int dgll_hip_gat_bwd_cols(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr, const int32_t* t_col,
-                          const int64_t* t_perm, const void* dn, int64_t ldn, const void* Hrow, int64_t ldh,
-                          const float* T_row, const float* S_col, const float* dd_col, const float* rowmax_col,
-                          const float* edge_scale, void* grad_H, int64_t ldgh, float* grad_T, int dtype,
-                          int64_t n_rows_t, int heads, int fo, float alpha, int mode, void* workspace, size_t workspace_bytes);
-
-/* sparseGatConv's form (mode 0, no attention dropout) with STRIDED score arrays -- the layout the gather passes are
- * fastest with.  These passes are bound by cache-line fills per edge: four for a 512-byte feature row plus one for every
- * separate per-node array gathered per edge.  So:
- *   T           is read at T[j * t_stride + head]: a compact [n_cols, heads] array (t_stride = heads), or a slot in the
- *               PADDING of the H rows themselves (a 47-class output row is 94 of 128 bytes: T = (float*)((char*)H + 96),
- *               t_stride = ldh * elem_size / 4) -- the score then shares the row's cache line and costs nothing;
- *   sd_scratch  fp32 scratch, sd_stride floats per destination row (>= 2 * heads): the rows pass leaves
- *               {s_i[0:heads], dd_i[0:heads]} side by side there and the transposed pass gathers both with ONE line fill
- *               -- a separate [n_rows, 2 * heads] buffer or a slot in the padding of the dn_scratch rows;
- *   T_rows      the compact [n_cols, heads] T for the row side of the transposed pass.
- * `fo` (per-head width) may be any multiple of the 16-byte vector (8 bf16 / 4 fp32 elements): a head that does not fill its
- * power-of-two lane group leaves lanes idle, no columns are padded.  Gradients w.r.t. H, S, T as dgll_hip_gat_bwd.      */
-int dgll_hip_gat_fwd_strided(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                             const void* H, int64_t ldh, const float* S, const float* T, int t_stride, void* out,
-                             int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int heads, int fo, float alpha,
-                             int apply_elu, void* workspace, size_t workspace_bytes);
-/* The forward pass with the gathered-side scores FORMED from the gathered rows: t_j = sum_f H[j, head fo + f] . attn2[head fo + f], as
- * sparseGatConv itself builds its logit from the gathered rows (gatconv.py:122-125) -- no score row is fetched per edge (one cache
- * line fewer per edge than dgll_hip_gat_fwd_strided when the rows fill their lines).  attn2: fp32 [heads * fo], a2 of every head laid
- * out like a row of H (bf16 storage: rounded to bf16 for the packed dot product, as the score product of the caller rounds it).  S as
- * before ([n_rows, heads] fp32).  raw / accumulate as dgll_hip_gat_fwd_ex.  sparseGatConv's form only (exp(-leakyrelu), no dropout).
- * n_cols = rows of H: the gathers use 32-bit byte offsets, so H may hold at most 2^24 rows and 4 GB (DGLL_ERR_UNSUPPORTED past
- * that: take dgll_hip_gat_fwd_strided).                                                                                         */
-int dgll_hip_gat_fwd_rowscore(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                              const void* H, int64_t ldh, const float* S, const float* attn2, void* out, int64_t ldo, int dtype,
-                              float* rowsum, int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu,
-                              void* workspace, size_t workspace_bytes, int raw, int accumulate);
-/* The rows pass of the backward in the same form (dgll_hip_gat_bwd_rows_strided with attn2 instead of T / t_stride; n_cols = rows of
- * H, bounded as above).                                                                                                          */
-int dgll_hip_gat_bwd_rows_rowscore(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                   const void* H, int64_t ldh, const float* S, const float* attn2,
-                                   const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                                   const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch, int sd_stride,
-                                   float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo, float alpha, int apply_elu,
-                                   void* workspace, size_t workspace_bytes);
-/* the two passes of dgll_hip_gat_bwd_strided one by one (rows of A: DN, {s, dd}, grad_S; then rows of A^T: grad_H, grad_T) */
-int dgll_hip_gat_bwd_rows_strided(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                  const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                                  const void* out, int64_t ldo, const void* grad_out, int64_t ldg, int dtype,
-                                  const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch, int sd_stride,
-                                  float* grad_S, int64_t n_rows, int heads, int fo, float alpha, int apply_elu,
-                                  void* workspace, size_t workspace_bytes);
-/* attn1 / attn2 / grad_S_rows (all three or none): when the scores are S = H.a1, T = H.a2 per head (gatconv.py:122-125), their
- * own contribution to grad_H is added in the epilogue -- grad_H[j, f] += grad_S[j, head(f)] * attn1[f] + grad_T[j, head(f)] *
- * attn2[f], attn* fp32 [heads * fo] laid out like a row of H, grad_S_rows fp32 [n_cols, heads] from the rows pass -- instead of
- * in a separate [n, 2 heads] x [2 heads, heads * fo] product and an add over [n, heads * fo].                              */
-int dgll_hip_gat_bwd_cols_strided(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
-                                  const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
-                                  int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
-                                  void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
-                                  int fo, float alpha, void* workspace, size_t workspace_bytes,
-                                  const float* attn1, const float* attn2, const float* grad_S_rows);
-/* The three strided passes with ATTENTION DROPOUT drawn in the kernels (gatconv.py:132: the row sum keeps every edge, the aggregation
- * loses a fraction p of them, survivors scaled by 1 / (1 - p)).  The multiplier of edge (row i, column j), head k is a pure function of
- * (seed, i, j, k) that each pass evaluates for the edges it walks -- no [nnz, heads] mask exists, forward or backward; the transposed
- * pass swaps the ids back.  Duplicate (i, j) entries of an adjacency that is not coalesced share a draw.
- *   p      in [0, 1): anything else is DGLL_ERR_INVALID;
- *   seed   DEVICE pointer to two 32-bit words, read by the kernels: a captured graph whose seed words are rewritten between replays
- *          draws a fresh mask on every replay.  The backward passes must be given the words the forward read.
- * Forward and rows pass: T (with t_stride) as dgll_hip_gat_fwd_strided, or NULL T and attn2 as dgll_hip_gat_fwd_rowscore (n_cols = rows
- * of H; node ids are 32-bit).  There is no in-row form with dropout: a T slot in the padding of the H rows is read as a strided
- * array.  Everything else as the entry points without dropout.                                                                   */
-int dgll_hip_gat_fwd_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                             const void* H, int64_t ldh, const float* S, const float* T, int t_stride, const float* attn2,
-                             void* out, int64_t ldo, int dtype, float* rowsum, int64_t n_rows, int64_t n_cols, int heads,
-                             int fo, float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
-                             const uint32_t* seed);
-int dgll_hip_gat_bwd_rows_dropout(void* stream, const dgll_csr_plan* plan, const int64_t* rowptr, const int32_t* col,
-                                  const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                                  const float* attn2, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
-                                  int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
-                                  int sd_stride, float* grad_S, int64_t n_rows, int64_t n_cols, int heads, int fo,
-                                  float alpha, int apply_elu, void* workspace, size_t workspace_bytes, double p,
-                                  const uint32_t* seed);
-int dgll_hip_gat_bwd_cols_dropout(void* stream, const dgll_csr_plan* t_plan, const int64_t* t_rowptr,
-                                  const int32_t* t_col, const void* dn_scratch, int64_t ldn, const void* H,
-                                  int64_t ldh, const float* T_rows, const float* sd_scratch, int sd_stride,
-                                  void* grad_H, int64_t ldgh, float* grad_T, int dtype, int64_t n_cols, int heads,
-                                  int fo, float alpha, void* workspace, size_t workspace_bytes,
-                                  const float* attn1, const float* attn2, const float* grad_S_rows, double p,
-                                  const uint32_t* seed);
-/* out[k * heads + h] = that multiplier for every nonzero k of a CSR and every head: fp32 [nnz, heads], exactly 0 or (float)(1 / (1 - p)).
+/* out[k * heads + h] = the dropout multiplier for every nonzero k of a CSR and every head: fp32 [nnz, heads], exactly 0 or (float)(1 / (1 - p)).
  * The device and the host form evaluate the same function and agree bit for bit (the host form takes host pointers and needs no GPU).
- * For tests and for callers that want the mask as an array (dgll_hip_gat_fwd's edge_scale); training never calls them.              */
+ * For tests and for callers that want the mask as an array (the edge_scale of dgll_hip_gat_pass); training never calls them.          */
 int dgll_hip_gat_dropout_mask(void* stream, const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads,
                               const uint32_t* seed, double p, float* out);
 int dgll_host_gat_dropout_mask(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int heads, const uint32_t* seed,
                                double p, float* out);
-int dgll_hip_gat_bwd_strided(void* stream, const dgll_csr_plan* plan, const dgll_csr_plan* t_plan,
-                             const int64_t* rowptr, const int32_t* col, const int64_t* t_rowptr, const int32_t* t_col,
-                             const void* H, int64_t ldh, const float* S, const float* T, int t_stride,
-                             const float* T_rows, const void* out, int64_t ldo, const void* grad_out, int64_t ldg,
-                             int dtype, const float* rowsum, void* dn_scratch, int64_t ldn, float* sd_scratch,
-                             int sd_stride, void* grad_H, int64_t ldgh, float* grad_S, float* grad_T, int64_t n_rows,
-                             int64_t n_cols, int heads, int fo, float alpha, int apply_elu, void* workspace,
-                             size_t workspace_bytes);
 
 /* ---- a10 / a4 as ONE launch: aggregate -> transform (bf16 storage, fp32 accumulation) ------------------------------------
  *   out[i, :] = act( A1[i, :K1] . W1 + reduce_{j in row i} X[j, :feat] . W2 + bias )

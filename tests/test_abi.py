@@ -31,7 +31,7 @@ def test_python_binding_covers_the_header():
 def test_abi_version_and_error_string():
     from dgll_amd import _lib
 
-    assert _lib.lib.dgll_hip_abi_version() == 1
+    assert _lib.lib.dgll_hip_abi_version() == 2
     assert isinstance(_lib.last_error(), str)
 
 

@@ -51,7 +51,7 @@ def test_kernel_fragments_name_the_instantiations(bench):
     assert bench.gat_kernel_fragment(1, 48, "torch.bfloat16", 0, packed=True) == "gat2_kernel<unsigned short, unsigned short, 8, 8, 1, 4, 0, true, false>"
     assert bench.gat_kernel_fragment(1, 48, "torch.bfloat16", 0, packed=False).endswith("0, false, false>")
     assert bench.gat_kernel_fragment(3, 24, "torch.bfloat16", 1) == "gat2_kernel<unsigned short, unsigned short, 8, 8, 2, 4, 1, false, false>"
-    # the 8-head forward in its row-score form (t_j from the gathered row: dgll_hip_gat_fwd_rowscore)
+    # the 8-head forward in its row-score form (t_j from the gathered row: attn2 instead of col_score)
     assert bench.gat_kernel_fragment(8, 32, "torch.bfloat16", 0, rowscore=True) == "gat2_kernel<unsigned short, unsigned short, 8, 32, 8, 4, 0, false, true>"
 
 

@@ -177,6 +177,8 @@ def test_passes_with_dropout_match_cpu_autograd_and_first_generation(cuda_device
 
 
 def test_entry_points_refuse_p_outside_the_unit_interval(cuda_device):
+    import ctypes
+
     from dgll_amd import _lib, ops
 
     _, g = _graph(cuda_device)
@@ -184,9 +186,14 @@ def test_entry_points_refuse_p_outside_the_unit_interval(cuda_device):
     h = torch.zeros(n, 8, device=cuda_device)
     s = torch.zeros(n, 1, device=cuda_device)
     out, rowsum, seed = torch.zeros_like(h), torch.zeros_like(s), _seed(cuda_device)
+    d = _lib.GatDesc()
+    d.pass_, d.dtype, d.apply_elu, d.rowptr, d.col, d.n_rows, d.n_cols = _lib.GAT_FORWARD, _lib.F32, 1, g.rowptr.data_ptr(), g.col.data_ptr(), n, n
+    d.heads, d.fo, d.alpha, d.h, d.ld_h, d.out, d.ld_out = 1, 8, 0.2, h.data_ptr(), 8, out.data_ptr(), 8
+    d.row_score = d.col_score = s.data_ptr()
+    d.col_score_stride, d.rowsum, d.drop_seed = 1, rowsum.data_ptr(), seed.data_ptr()
     for bad in (1.0, -0.25, float("nan")):
-        code = _lib.lib.dgll_hip_gat_fwd_dropout(None, None, g.rowptr.data_ptr(), g.col.data_ptr(), h.data_ptr(), 8, s.data_ptr(), s.data_ptr(), 1,
-                                                 None, out.data_ptr(), 8, 0, rowsum.data_ptr(), n, n, 1, 8, 0.2, 1, None, 0, bad, seed.data_ptr())
+        d.drop_p = bad
+        code = _lib.lib.dgll_hip_gat_pass(None, ctypes.byref(d))
         assert code == -1 and "[0, 1)" in _lib.last_error()
     with pytest.raises(ValueError):
         ops.gat_aggregate(g, h, s, s, 1, 0.2, dropout_p=1.0)

@@ -90,7 +90,7 @@ def test_gat_layer_node_equals_the_separate_nodes(cuda_device):
 @pytest.mark.parametrize("heads,fo,dtype", [(8, 32, torch.bfloat16), (3, 24, torch.bfloat16), (2, 16, torch.bfloat16), (4, 32, torch.float32),
                                             (8, 8, torch.float32), (2, 64, torch.float32), (1, 40, torch.float32)])
 def test_row_score_passes_equal_the_gathered_score_passes(cuda_device, heads, fo, dtype, monkeypatch):
-    """dgll_hip_gat_fwd_rowscore / dgll_hip_gat_bwd_rows_rowscore (t_j formed from the gathered row; 32-bit gather offsets; one
+    """The row-score form of the forward and of the rows pass (t_j formed from the gathered row; 32-bit gather offsets; one
     exponential per lane and four edges where a head has four lanes; heads that leave lanes of their group idle) against the passes
     that gather T: same outputs and gradients, fp32 to rounding, bf16 to its storage rounding.  A rows-long row (long-row chunks)
     rides along."""
@@ -137,18 +137,33 @@ def test_row_score_passes_equal_the_gathered_score_passes(cuda_device, heads, fo
 
 
 def test_row_score_entry_points_refuse_what_32_bit_offsets_cannot_address(cuda_device):
-    """Both row-score entry points address the gathered rows by 32-bit byte offsets: more than 2^24 rows, or more than 4 GB, is
-    DGLL_ERR_UNSUPPORTED with a message naming the form to take (checked before anything is launched: dummy pointers)."""
+    """The row-score form of the forward and of the rows pass addresses the gathered rows by 32-bit byte offsets: more than 2^24 rows,
+    or more than 4 GB, is DGLL_ERR_UNSUPPORTED with a message naming the field to fill instead (checked before anything is launched:
+    dummy pointers)."""
+    import ctypes
+
     from dgll_amd import _lib
 
     one = torch.zeros(64, device=cuda_device)
     p = one.data_ptr()
+
+    def desc(kind, dtype, ld, n_cols, fo):
+        d = _lib.GatDesc()
+        d.pass_, d.dtype, d.apply_elu, d.rowptr, d.col, d.n_rows, d.n_cols = kind, dtype, 1, p, p, 10, n_cols
+        d.heads, d.fo, d.alpha = 8, fo, 0.2
+        d.h = d.out = d.row_score = d.attn2 = d.rowsum = p
+        d.ld_h = d.ld_out = ld
+        return d
+
     # (DGLL_ERR_UNSUPPORTED = -3, include/dgll_hip.h)
-    too_many_rows = _lib.lib.dgll_hip_gat_fwd_rowscore(None, None, p, p, p, 256, p, p, p, 256, 1, p, 10, (1 << 24) + 1, 8, 32, 0.2, 1, None, 0, 0, 0)
-    assert too_many_rows == -3 and b"dgll_hip_gat_fwd_strided" in _lib.lib.dgll_hip_last_error()
-    too_large = _lib.lib.dgll_hip_gat_bwd_rows_rowscore(None, None, p, p, p, 1024, p, p, p, 1024, p, 1024, 0, p, p, 1024, p, 16, p, 10,
-                                                        (1 << 21), 8, 128, 0.2, 1, None, 0)        # 2 M rows x 4 KB = 8 GB
-    assert too_large == -3 and b"dgll_hip_gat_bwd_rows_strided" in _lib.lib.dgll_hip_last_error()
+    fwd = desc(_lib.GAT_FORWARD, _lib.BF16, 256, (1 << 24) + 1, 32)
+    too_many_rows = _lib.lib.dgll_hip_gat_pass(None, ctypes.byref(fwd))
+    assert too_many_rows == -3 and b"col_score" in _lib.lib.dgll_hip_last_error()
+    rows = desc(_lib.GAT_ROWS, _lib.F32, 1024, 1 << 21, 128)        # 2 M rows x 4 KB = 8 GB
+    rows.grad_out = rows.dn = rows.sd = rows.grad_score = p
+    rows.ld_grad_out, rows.ld_dn, rows.sd_stride, rows.phase = 1024, 1024, 16, _lib.GAT_ROWS_EXACT_ONLY
+    too_large = _lib.lib.dgll_hip_gat_pass(None, ctypes.byref(rows))
+    assert too_large == -3 and b"col_score" in _lib.lib.dgll_hip_last_error()
 
 
 def test_bf16_spgat_bench_configuration_against_the_storage_emulating_oracle(cuda_device):

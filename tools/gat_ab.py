@@ -69,19 +69,17 @@ for gen in gens:
     print("gen %d: fwd %.3f ms (%.2fx spmm, alg %.0f GB/s = %.2f of 8 TB/s) | bwd_rows %.3f ms (%.2fx) | "
           "bwd_cols (separate S, DD arrays) %.3f ms (%.2fx)" % (gen, f, f / base, b_alg / f / 1e6, b_alg / f / 1e6 / 8000, r, r / base,
                                                                c, c / base), flush=True)
-    if gen == 0:   # both backward passes through the strided entry point ({s, dd} side by side): cols = total - rows
-        ws_bytes = max(int(_lib.lib.dgll_hip_gat_workspace_bytes(g.plan(), heads, fo)),
-                       int(_lib.lib.dgll_hip_gat_workspace_bytes(gt.plan(), heads, fo)))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
+    if gen == 0:   # both backward passes in the strided form ({s, dd} side by side): cols = total - rows
+        ws = ops_edge._ws(g.plan(), heads, fo, dev, gt.plan())
 
         def both():
-            code = _lib.lib.dgll_hip_gat_bwd_strided(
-                st, g.plan(), gt.plan(), g.rowptr.data_ptr(), g.col.data_ptr(), gt.rowptr.data_ptr(), gt.col.data_ptr(),
-                h.data_ptr(), h.stride(0), s.data_ptr(), t.data_ptr(), heads, t.data_ptr(), out.data_ptr(), out.stride(0),
-                go.data_ptr(), go.stride(0), _lib.BF16, rowsum.data_ptr(), dn.data_ptr(), dn.stride(0), sd.data_ptr(), 2 * heads,
-                gh.data_ptr(), gh.stride(0), gs.data_ptr(), gtt.data_ptr(), n, n, heads, fo, 0.2, 1, ws.data_ptr(), ws_bytes)
-            _lib.check(code, "dgll_hip_gat_bwd_strided")
+            ops_edge._gat_pass(_lib.GAT_ROWS, g, heads, fo, 0.2, h, apply_elu=1, ws=ws, phase=_lib.GAT_ROWS_EXACT_ONLY, row_score=s.data_ptr(),
+                               col_score=t.data_ptr(), col_score_stride=heads, out=out.data_ptr(), ld_out=out.stride(0),
+                               grad_out=go.data_ptr(), ld_grad_out=go.stride(0), rowsum=rowsum.data_ptr(), dn=dn.data_ptr(),
+                               ld_dn=dn.stride(0), sd=sd.data_ptr(), sd_stride=2 * heads, grad_score=gs.data_ptr())
+            ops_edge._gat_pass(_lib.GAT_TRANSPOSED, gt, heads, fo, 0.2, h, ws=ws, dn=dn.data_ptr(), ld_dn=dn.stride(0),
+                               row_score=t.data_ptr(), col_score=sd.data_ptr(), col_dd=sd.data_ptr() + 4 * heads,
+                               col_score_stride=2 * heads, grad_h=gh.data_ptr(), ld_grad_h=gh.stride(0), grad_score=gtt.data_ptr())
 
         bt = timeit(both)
         print("gen 0: both backward passes, {s, dd} side by side: %.3f ms -> bwd_cols %.3f ms (%.2fx)" % (bt, bt - r, (bt - r) / base),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of the GAT forward pass at the config-4 shape (8 heads x 32 bf16, products-sized graph + self-loops, engine reorder):
-dgll_hip_gat_fwd_strided (T[j] gathered per edge: a fifth cache line next to the four of the 512-byte row) against
-dgll_hip_gat_fwd_rowscore (t_j = h_j . a2 formed from the gathered row), next to the SpMM at the same width.  Kill criterion of
+col_score given (T[j] gathered per edge: a fifth cache line next to the four of the 512-byte row) against the row-score form
+(attn2 instead of col_score: t_j = h_j . a2 formed from the gathered row), next to the SpMM at the same width.  Kill criterion of
 VERDICT r05 item 3: the row-score forward must come in under 5.1 ms.  Also prints the largest output difference between the forms.
 
     python tools/gat_rowscore_ab.py [locality] [dtype: bf16|f32]
@@ -46,7 +46,7 @@ def timeit(fn, reps=10):
 base = timeit(lambda: ops.spmm_raw(g, h, reduce="mean"))
 print("spmm mean unweighted, F = %d %s: %.3f ms" % (F, dtype, base))
 res = {}
-for name, flag in (("T gathered (dgll_hip_gat_fwd_strided)", False), ("t_j from the gathered row (dgll_hip_gat_fwd_rowscore)", True)):
+for name, flag in (("T gathered (col_score)", False), ("t_j from the gathered row (attn2)", True)):
     ops_edge.ROW_SCORES = flag
     out = ops_edge._gat_strided_forward(h, s, t, g, heads, fo, 0.2, 1, False, attn2=a2)
     ms = timeit(lambda: ops_edge._gat_strided_forward(h, s, t, g, heads, fo, 0.2, 1, False, attn2=a2))
