@@ -124,6 +124,19 @@ TYPED_COEFF_LDS = 4096      # DGLL_TYPED_COEFF_LDS: the coefficient table is sta
 TYPED_BASIS_BLOCK = 8       # DGLL_TYPED_BASIS_BLOCK: bases a launch block accumulates at the most
 
 
+class MpDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_mp_desc (dgll_hip_mp_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("heads", C.c_int), ("D", C.c_int),
+                ("e", C.c_void_p), ("ld_e", C.c_int64), ("e2", C.c_void_p), ("ld_e2", C.c_int64), ("e_out", C.c_void_p), ("ld_e_out", C.c_int64),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("y", C.c_void_p), ("ld_y", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64)]
+
+
+MP_EDGE_SOFTMAX, MP_EDGE_SOFTMAX_BWD, MP_E_SUM, MP_U_ADD_V, MP_U_MUL_E_SUM, MP_U_DOT_V = range(6)
+MP_LONG_ROW = 256           # DGLL_MP_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -269,6 +282,7 @@ SIGNATURES = {
     "dgll_hip_gatv2_pass": (_i32, [_vp, C.POINTER(Gatv2Desc)]),
     "dgll_hip_sparse_attn_pass": (_i32, [_vp, C.POINTER(AttnDesc)]),
     "dgll_hip_typed_spmm_pass": (_i32, [_vp, C.POINTER(TypedDesc)]),
+    "dgll_hip_mp_pass": (_i32, [_vp, C.POINTER(MpDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

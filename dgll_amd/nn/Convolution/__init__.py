@@ -9,7 +9,8 @@ from .gatv2conv import GATv2Conv, GATv2
 from .dotgatconv import DotGatConv
 from .transformerconv import TransformerConv, GraphTransformer
 from .relgraphconv import RelGraphConv, RGCN
+from .agnnconv import AGNNConv, AGNN
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
-           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN"]
+           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN"]

@@ -16,7 +16,9 @@ whose width is not a whole number of 16-byte vectors are padded with zero rows i
 the scale stays that of the true head width.  Host tensors take `_host_aggregate`, the same semantics with torch's segment ops, so
 that the layer's own logic can be exercised without a GPU; a GPU tensor never reaches it.
 
-get_attention=True raises NotImplementedError: the attention weights are never formed per edge.
+get_attention=True raises NotImplementedError: the attention weights are never formed per edge.  Where they are wanted, the general
+path forms them: dgll_amd.ops_mp (`edge_softmax(graph, scale * u_dot_v(graph, k, q, heads))`, then `u_mul_e_sum`), at the price of
+[nnz, heads] fp32 tensors.
 """
 from ... import backend as F
 from ... import dense, ops, ops_attn

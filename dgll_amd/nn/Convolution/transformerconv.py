@@ -20,7 +20,9 @@ fused gather passes (ops_attn.sparse_attention): no [nnz, heads] tensor exists. 
 the true head width.  Host tensors take the torch segment-op path of dotgatconv._host_aggregate.
 
 Not built: attention dropout inside the gather kernels (dropout != 0 raises, as GATv2Conv.attn_drop does) and edge features
-(edge_dim is not None raises: they would need an [nnz, heads * out_channels] tensor).
+(edge_dim is not None raises: they would need an [nnz, heads * out_channels] tensor).  A layer that needs something per edge can be
+written on the general path, dgll_amd.ops_mp (u_dot_v, u_add_v, edge_softmax, u_mul_e_sum, copy_e_sum: per-edge tensors with
+autograd), which pays [nnz, heads] fp32 per tensor for it.
 """
 from ... import backend as F
 from ... import dense, ops, ops_attn

@@ -993,6 +993,41 @@ typedef struct dgll_typed_desc {
 } dgll_typed_desc;
 int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d);
 
+/* ---- Per-edge message passing (DGL's edge_softmax, u_mul_e_sum, u_dot_v, u_add_v, copy_e_sum): six passes behind one entry point
+ * (csrc/mp_ops.hip).  The general path under the fused layers: per-edge tensors EXIST here, fp32 [nnz, heads] each.
+ * Entry k of the pass's CSR (rowptr / col: n_rows rows gathering from n_cols; rectangular allowed, duplicate entries are separate
+ * edges) belongs to row i(k) and addresses the per-edge arrays at slot s(k) = perm ? perm[k] : k.  With perm (A^T's entry -> A's
+ * entry, graph.transpose()) a pass runs over A^T while the per-edge data stays in A's entry order; `nnz` is the number of rows of
+ * the per-edge arrays.  perm and col values used for addressing are clamped to [0, nnz) and [0, n_cols).  Per head h:
+ *   DGLL_MP_EDGE_SOFTMAX      e_out[s(k), h] = exp(e[s(k), h] - m_ih) / l_ih over the entries of row i (max-subtracted).  An entry
+ *                             of -inf gives 0; a row of -inf alone, like an empty row, writes zeros and never NaN.
+ *   DGLL_MP_EDGE_SOFTMAX_BWD  e = alpha (the forward's output), e2 = grad: e_out[s, h] = alpha (g - sum_row alpha g), the row sum in fp32.
+ *   DGLL_MP_E_SUM             out[i, h] = sum_k e[s(k), h]; out fp32 [n_rows, heads] (an empty row: 0); dtype must be DGLL_F32.
+ *   DGLL_MP_U_ADD_V           e_out[s(k), h] = x[col_k, h] + y[i(k), h]; x [n_cols, heads] and y [n_rows, heads] fp32, either may be
+ *                             NULL (0; col is read only with x); dtype must be DGLL_F32.
+ *   DGLL_MP_U_MUL_E_SUM       out[i, h*D : (h+1)*D] = sum_k e[s(k), h] * x[col_k, h*D : (h+1)*D]; x and out of `dtype` (an empty row: 0).
+ *   DGLL_MP_U_DOT_V           e_out[s(k), h] = <x[col_k, h, :], y[i(k), h, :]>; x and y of `dtype`, products and sum in fp32.
+ * Per-edge arrays are always fp32 with pitches ld_e* >= heads, any heads >= 1 (D is not read by the first four passes).  The node
+ * matrices of the last two are of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation), pitches in elements: whole 16-byte vectors,
+ * 16-byte aligned bases; D a multiple of the vector width (4 fp32 / 8 bf16 columns), at most 64 vectors.  Rows longer than
+ * DGLL_MP_LONG_ROW entries are swept by a whole workgroup.  No float atomics: two runs give the same bits.  No pass allocates,
+ * synchronises or reads anything back: the calls can be captured into a graph.  n_rows == 0 launches nothing.                     */
+enum { DGLL_MP_EDGE_SOFTMAX = 0, DGLL_MP_EDGE_SOFTMAX_BWD = 1, DGLL_MP_E_SUM = 2,
+       DGLL_MP_U_ADD_V = 3, DGLL_MP_U_MUL_E_SUM = 4, DGLL_MP_U_DOT_V = 5 };
+#define DGLL_MP_LONG_ROW 256
+typedef struct dgll_mp_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int heads; int D;
+    const float* e;  int64_t ld_e;
+    const float* e2; int64_t ld_e2;
+    float* e_out;    int64_t ld_e_out;
+    const void* x; int64_t ld_x;
+    const void* y; int64_t ld_y;
+    void* out; int64_t ld_out;
+} dgll_mp_desc;
+int dgll_hip_mp_pass(void* stream, const dgll_mp_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
