@@ -22,6 +22,7 @@ _ALIASES = {
     "dgll.nn.Convolution.transformerconv": "dgll_amd.nn.Convolution.transformerconv",
     "dgll.nn.Convolution.relgraphconv": "dgll_amd.nn.Convolution.relgraphconv",
     "dgll.nn.Convolution.agnnconv": "dgll_amd.nn.Convolution.agnnconv",
+    "dgll.nn.Convolution.pnaconv": "dgll_amd.nn.Convolution.pnaconv",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",

@@ -137,6 +137,23 @@ MP_EDGE_SOFTMAX, MP_EDGE_SOFTMAX_BWD, MP_E_SUM, MP_U_ADD_V, MP_U_MUL_E_SUM, MP_U
 MP_LONG_ROW = 256           # DGLL_MP_LONG_ROW of include/dgll_hip.h
 
 
+class MultiAggDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_multi_agg_desc (dgll_hip_multi_agg_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64), ("F", C.c_int64),
+                ("n_agg", C.c_int), ("agg", C.c_int * 6), ("n_scaler", C.c_int), ("scaler", C.c_int * 3), ("delta", C.c_float),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("y", C.c_void_p), ("ld_y", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("stats", C.c_void_p), ("ld_stats", C.c_int64),
+                ("arg", C.c_void_p), ("ld_arg", C.c_int64), ("coef", C.c_void_p), ("ld_coef", C.c_int64),
+                ("grad_y", C.c_void_p), ("ld_grad_y", C.c_int64), ("grad_x", C.c_void_p), ("ld_grad_x", C.c_int64)]
+
+
+MAGG_FORWARD, MAGG_ROWS, MAGG_COLS = 0, 1, 2
+MAGG_MEAN, MAGG_SUM, MAGG_MAX, MAGG_MIN, MAGG_VAR, MAGG_STD = range(6)
+MAGG_IDENTITY, MAGG_AMPLIFICATION, MAGG_ATTENUATION = 0, 1, 2
+MAGG_LONG_ROW = 256         # DGLL_MAGG_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -283,6 +300,7 @@ SIGNATURES = {
     "dgll_hip_sparse_attn_pass": (_i32, [_vp, C.POINTER(AttnDesc)]),
     "dgll_hip_typed_spmm_pass": (_i32, [_vp, C.POINTER(TypedDesc)]),
     "dgll_hip_mp_pass": (_i32, [_vp, C.POINTER(MpDesc)]),
+    "dgll_hip_multi_agg_pass": (_i32, [_vp, C.POINTER(MultiAggDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

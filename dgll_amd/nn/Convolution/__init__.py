@@ -10,7 +10,9 @@ from .dotgatconv import DotGatConv
 from .transformerconv import TransformerConv, GraphTransformer
 from .relgraphconv import RelGraphConv, RGCN
 from .agnnconv import AGNNConv, AGNN
+from .pnaconv import PNAConv, PNA
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
-           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN"]
+           "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN",
+           "PNAConv", "PNA"]

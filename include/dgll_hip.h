@@ -1028,6 +1028,58 @@ typedef struct dgll_mp_desc {
 } dgll_mp_desc;
 int dgll_hip_mp_pass(void* stream, const dgll_mp_desc* d);
 
+/* ---- Multi-aggregator gather (PNA / DGL's PNAConv): several reductions of a neighbourhood from ONE gather, three passes behind one
+ * entry point (csrc/multi_agg.hip).  rowptr / col: a CSR matrix [n_rows x n_cols] (rectangular allowed; edge values are not read;
+ * duplicate entries are separate edges).  The descriptor carries the ORDERED lists the caller asked for: n_agg <= 6 aggregator codes
+ * agg[] and n_scaler <= 3 scaler codes scaler[], no repeats.  Over the D_i entries j of row i, x the gathered matrix [n_cols, F] and y
+ * an optional per-row addend [n_rows, F] (NULL: 0):
+ *     DGLL_MAGG_MEAN  mean_j x[j] + y[i]           DGLL_MAGG_SUM  sum_j x[j] + D_i y[i]
+ *     DGLL_MAGG_MAX   max_j x[j] + y[i]            DGLL_MAGG_MIN  min_j x[j] + y[i]
+ *     DGLL_MAGG_VAR   relu(mean_j x[j]^2 - (mean_j x[j])^2)   (y does not enter)        DGLL_MAGG_STD  sqrt(VAR + 1e-30)
+ * and the per-row scalers, delta > 0:  DGLL_MAGG_IDENTITY 1, DGLL_MAGG_AMPLIFICATION log(D_i + 1) / delta, DGLL_MAGG_ATTENUATION
+ * delta / log(D_i + 1).  A row WITHOUT entries writes zeros in every block (y and the scalers do not apply).  The variance is
+ * accumulated about the row's first entry: a row whose entries are all equal gives exactly VAR = 0 and STD = sqrt(1e-30).
+ *   DGLL_MAGG_FORWARD  rowptr / col = A.  Reads x and optionally y; writes out [n_rows, n_scaler * n_agg * F] of `dtype`, block
+ *                      (s * n_agg + a) = scaler_s(i) * agg_a(i) (DGL's concatenation order); optionally stats fp32 [n_rows, 2 F]:
+ *                      mean | variance of x over the row (without y), and arg int32 [n_rows, 2 F]: the source row attaining the
+ *                      max | min per column, -1 for an empty row.  TIES: among the entries attaining the extreme, the smallest
+ *                      source id (torch gives the gradient to an unspecified one of them: the results differ on ties only).
+ *   DGLL_MAGG_ROWS     no gather.  Reads grad_out (the shape of out), rowptr and stats (required with coef when VAR or STD is
+ *                      asked); folds the scalers and writes coef fp32 [n_rows, 5 F] = c0 | c1 | mean | g_max | g_min with
+ *                      c0 = g_sum + g_mean / D_i and c1 = (2 g_var + g_std / std_i) / D_i where var_i > 0, EXACTLY 0 elsewhere; and
+ *                      grad_y [n_rows, F] of `dtype` = g_mean + g_max + g_min + D_i g_sum (0 for an empty row).  Either output may be
+ *                      NULL, not both.
+ *   DGLL_MAGG_COLS     rowptr / col = A^T with sorted rows (n_rows = A's n_cols).  Reads x [n_rows, F] (held), coef and arg of A's
+ *                      rows; writes grad_x [n_rows, F] of `dtype` (zeros for a source no row references):
+ *                          grad_x[j] = sum_{i in row j} c0_i + c1_i (x[j] - mean_i) + (argmax_i == j) g_max_i + (argmin_i == j) g_min_i
+ *                      the variance term formed per entry; a repeated (j, i) pair counts once for max / min, as in
+ *                      dgll_hip_segment_max_bwd.  arg is required when MAX or MIN is asked.
+ * Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation), pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned
+ * bases; stats, arg and coef likewise (pitches multiples of 4).  F a positive multiple of the vector width (4 fp32 / 8 bf16 columns);
+ * widths past 64 vectors go to column blocks.  Indices used for addressing are clamped.  Rows longer than DGLL_MAGG_LONG_ROW entries
+ * are swept by a whole workgroup and merged through LDS in group order.  No atomics: two runs give the same bits.  No pass allocates,
+ * synchronises or reads anything back: the calls can be captured into a graph.  n_rows == 0 launches nothing.                       */
+enum { DGLL_MAGG_FORWARD = 0, DGLL_MAGG_ROWS = 1, DGLL_MAGG_COLS = 2 };
+enum { DGLL_MAGG_MEAN = 0, DGLL_MAGG_SUM = 1, DGLL_MAGG_MAX = 2, DGLL_MAGG_MIN = 3, DGLL_MAGG_VAR = 4, DGLL_MAGG_STD = 5 };
+enum { DGLL_MAGG_IDENTITY = 0, DGLL_MAGG_AMPLIFICATION = 1, DGLL_MAGG_ATTENUATION = 2 };
+#define DGLL_MAGG_LONG_ROW 256
+typedef struct dgll_multi_agg_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; int64_t n_rows; int64_t n_cols;
+    int64_t F;
+    int n_agg; int agg[6]; int n_scaler; int scaler[3]; float delta;
+    const void* x; int64_t ld_x;
+    const void* y; int64_t ld_y;
+    void* out; int64_t ld_out;
+    const void* grad_out; int64_t ld_grad_out;
+    float* stats; int64_t ld_stats;
+    int32_t* arg; int64_t ld_arg;
+    float* coef; int64_t ld_coef;
+    void* grad_y; int64_t ld_grad_y;
+    void* grad_x; int64_t ld_grad_x;
+} dgll_multi_agg_desc;
+int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
