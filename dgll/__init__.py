@@ -23,6 +23,8 @@ _ALIASES = {
     "dgll.nn.Convolution.relgraphconv": "dgll_amd.nn.Convolution.relgraphconv",
     "dgll.nn.Convolution.agnnconv": "dgll_amd.nn.Convolution.agnnconv",
     "dgll.nn.Convolution.pnaconv": "dgll_amd.nn.Convolution.pnaconv",
+    "dgll.nn.Convolution.gineconv": "dgll_amd.nn.Convolution.gineconv",
+    "dgll.nn.Convolution.cfconv": "dgll_amd.nn.Convolution.cfconv",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",

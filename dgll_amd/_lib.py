@@ -154,6 +154,21 @@ MAGG_IDENTITY, MAGG_AMPLIFICATION, MAGG_ATTENUATION = 0, 1, 2
 MAGG_LONG_ROW = 256         # DGLL_MAGG_LONG_ROW of include/dgll_hip.h
 
 
+class EdgeFeatDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_edge_feat_desc (dgll_hip_edge_feat_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int), ("op", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("F", C.c_int64), ("scale", C.c_void_p),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("e", C.c_void_p), ("ld_e", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("grad_x", C.c_void_p), ("ld_grad_x", C.c_int64), ("grad_e", C.c_void_p), ("ld_grad_e", C.c_int64)]
+
+
+EF_FORWARD, EF_COLS, EF_EDGE = 0, 1, 2
+EF_ADD, EF_ADD_RELU, EF_MUL = 0, 1, 2
+EF_LONG_ROW = 256           # DGLL_EF_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -301,6 +316,7 @@ SIGNATURES = {
     "dgll_hip_typed_spmm_pass": (_i32, [_vp, C.POINTER(TypedDesc)]),
     "dgll_hip_mp_pass": (_i32, [_vp, C.POINTER(MpDesc)]),
     "dgll_hip_multi_agg_pass": (_i32, [_vp, C.POINTER(MultiAggDesc)]),
+    "dgll_hip_edge_feat_pass": (_i32, [_vp, C.POINTER(EdgeFeatDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -11,8 +11,10 @@ from .transformerconv import TransformerConv, GraphTransformer
 from .relgraphconv import RelGraphConv, RGCN
 from .agnnconv import AGNNConv, AGNN
 from .pnaconv import PNAConv, PNA
+from .gineconv import GINEConv, GINE
+from .cfconv import CFConv, ShiftedSoftplus
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
            "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN",
-           "PNAConv", "PNA"]
+           "PNAConv", "PNA", "GINEConv", "GINE", "CFConv", "ShiftedSoftplus"]

@@ -1080,6 +1080,46 @@ typedef struct dgll_multi_agg_desc {
 } dgll_multi_agg_desc;
 int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d);
 
+/* ---- Edge-feature aggregation (DGL's GINEConv, CFConv): a gather-reduce whose message combines the gathered source row with a
+ * per-edge row of the SAME width, and its exact backward; three passes behind one entry point (csrc/edge_feat.hip).  Entry k of row
+ * i of A (rowptr / col, [n_dst x n_src], rectangular allowed, edge values are not read) is the edge j = col[k] -> i and e[k, :] its
+ * feature row, in A's entry order; duplicate entries are separate edges with their own rows.  scale: an optional fp32 factor s_i per
+ * DESTINATION row (NULL: 1; the mean reduce passes 1 / D_i, 0 for an empty row).  op chooses the message:
+ *     DGLL_EF_ADD       m = x_j + e_k          dm/dx = 1        dm/de = 1
+ *     DGLL_EF_ADD_RELU  m = relu(x_j + e_k)    dm/dx = gate_k   dm/de = gate_k      gate_k = (x_j + e_k > 0)
+ *     DGLL_EF_MUL       m = x_j * e_k          dm/dx = e_k      dm/de = x_j
+ * The gate is recomputed from the stored operands as the same fp32 sum in every pass and never stored.
+ *   DGLL_EF_FORWARD  rowptr / col = A (n_rows = n_dst, n_cols = n_src).  out[i] = s_i * sum_k m(x[col_k], e[k]); reads x [n_cols, F]
+ *                    (gathered), e [nnz, F] (streamed at slot k), scale [n_rows]; writes out [n_rows, F] (an empty row: zeros).
+ *   DGLL_EF_COLS     rowptr / col = A^T (n_rows = n_src, n_cols = n_dst) with perm, A^T's entry k' -> A's entry (graph.transpose()).
+ *                    grad_x[j] = sum_k' s_i dm/dx grad_out[i], i = col[k']; reads grad_out [n_cols, F] (gathered), scale [n_cols]
+ *                    (by the gathered row), x [n_rows, F] (held; ADD_RELU only), e at slot perm[k'] (ADD_RELU and MUL; perm is then
+ *                    required); writes grad_x [n_rows, F] (zeros for a source no row references).
+ *   DGLL_EF_EDGE     rowptr / col = A.  grad_e[k] = s_i dm/de grad_out[i]; reads grad_out [n_rows, F] (held), x gathered (ADD_RELU
+ *                    and MUL), e at slot k (ADD_RELU); writes grad_e [nnz, F] of `dtype`.  No reduction.
+ * Operands a (pass, op) does not read may be NULL and are not dereferenced.  nnz: the rows of e / grad_e (perm values are clamped
+ * to [0, nnz), col values used for addressing to [0, n_cols)).  Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation),
+ * pitches ld_* in elements, each its own: whole 16-byte vectors >= F, 16-byte aligned bases.  F a positive multiple of the vector
+ * width (4 fp32 / 8 bf16 columns); widths past 64 vectors go to column blocks.  Rows longer than DGLL_EF_LONG_ROW entries are swept
+ * by a whole workgroup and, where there is a sum, merged through LDS in group order.  No atomics: two runs give the same bits.  No
+ * pass allocates, synchronises or reads anything back: the calls can be captured into a graph.  n_rows == 0 launches nothing.       */
+enum { DGLL_EF_FORWARD = 0, DGLL_EF_COLS = 1, DGLL_EF_EDGE = 2 };
+enum { DGLL_EF_ADD = 0, DGLL_EF_ADD_RELU = 1, DGLL_EF_MUL = 2 };
+#define DGLL_EF_LONG_ROW 256
+typedef struct dgll_edge_feat_desc {
+    int pass; int dtype; int op;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int64_t F;
+    const float* scale;
+    const void* x; int64_t ld_x;
+    const void* e; int64_t ld_e;
+    const void* grad_out; int64_t ld_grad_out;
+    void* out; int64_t ld_out;
+    void* grad_x; int64_t ld_grad_x;
+    void* grad_e; int64_t ld_grad_e;
+} dgll_edge_feat_desc;
+int dgll_hip_edge_feat_pass(void* stream, const dgll_edge_feat_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
