@@ -85,3 +85,47 @@ def test_kernel_source_in_lock_step(emulator, tmp_path, heads, D, dtype):
             assert ((a - b).norm() / b.norm()).item() <= 1.5e-2, name
     assert got[0][0].abs().max().item() == 0.0 and got[0][-1].abs().max().item() == 0.0         # the empty rows
     assert got[1][-1].abs().max().item() == 0.0                                                 # the unreferenced source
+
+
+# The closed-form legs of rowtile_ref.py on the source (cut-down graph: rows of 0, 1, 7 .. 9, 63 .. 65, 255 .. 257 and 400 distinct
+# entries): 3 x 24 bf16 = 3 of 4 lanes a head, 12 of 16 lanes a row; 5 x 8 fp32 = 5 heads of 2 lanes in 16 (3 idle heads);
+# 33 x 8 fp32 = two column blocks of 32 heads of 2 lanes, the second with one head.  One dattn partial: every tile grid-stride in one workgroup.
+@pytest.mark.parametrize("leg", ["flat", "onehot"])
+@pytest.mark.parametrize("heads,D,dtype", [(3, 24, torch.bfloat16), (5, 8, torch.float32), (33, 8, torch.float32)],
+                         ids=lambda v: str(v).replace("torch.", ""))
+def test_closed_form_legs_in_lock_step(emulator, tmp_path, heads, D, dtype, leg):
+    import rowtile_ref as R
+
+    graph = R.emu_graph()
+    case = R.Case(dtype, heads, D, None)
+    xl, xr, attn, g, slope = R.gatv2_operands(graph, case, leg)
+    F, d = heads * D, str(tmp_path)
+    gt, _ = graph.csr().transpose()
+    for name, t in (("rowptr", graph.rowptr), ("col", graph.col), ("trowptr", gt.rowptr), ("tcol", gt.col), ("xl", xl), ("xr", xr),
+                    ("g", g), ("attn", attn)):
+        _dump(t, os.path.join(d, name + ".bin"))
+    res = subprocess.run([emulator, d, str(graph.n_rows), str(graph.n_cols), str(heads), str(D), "0" if dtype == torch.float32 else "1",
+                          repr(slope), "1"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "emu ok" in res.stdout, res.stdout + res.stderr
+    got = {"out": _read(os.path.join(d, "out.bin"), dtype, (graph.n_rows, F)), "dxl": _read(os.path.join(d, "dxl.bin"), dtype, (graph.n_cols, F)),
+           "dxr": _read(os.path.join(d, "dxr.bin"), dtype, (graph.n_rows, F)), "dattn": _read(os.path.join(d, "dattn.bin"), torch.float32, (1, F))}
+    lse = _read(os.path.join(d, "lse.bin"), torch.float32, (graph.n_rows, heads))
+    ref = R.gatv2_reference(graph, xl, xr, attn, g, heads, slope)
+    empty = np.flatnonzero(graph.deg == 0)
+    bad = R.check_finite("out", got["out"]) + R.check_finite("lse", lse) + R.check_zero_rows("out", got["out"], empty) \
+        + R.check_zero_rows("lse", lse, empty)
+    if leg == "onehot":
+        win, mult, top = R.winners(graph, ref["s"])
+        want, keep = R.onehot_expected(graph, xl, win, mult, heads)
+        assert bool(keep.all())
+        bad += R.check_equal("out", got["out"], want, keep, heads)
+        bad += R.check_lse("lse", lse, *R.onehot_lse(top, mult))[0]
+    else:
+        bad += R.check_flat_forward("out", got["out"], ref["mean"])[0]
+        bad += R.check_lse("lse", lse, ref["lse"], R.flat_lse_bar(graph, ref))[0]
+        for name in ("dxl", "dxr", "dattn"):
+            found, frac = R.check_units(name, got[name], ref[name])
+            print("%s %dx%d %s: %.3f of the bar" % (leg, heads, D, name, frac))
+            bad += found + R.check_finite(name, got[name])
+        bad += R.check_zero_rows("dxr", got["dxr"], empty) + R.check_zero_rows("dxl", got["dxl"], graph.unreferenced)
+    assert not bad, "\n".join(bad)

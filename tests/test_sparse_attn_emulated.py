@@ -89,3 +89,49 @@ def test_kernel_source_in_lock_step(emulator, tmp_path, heads, D, dtype, shared)
     assert got[2][-1].abs().max().item() == 0.0 and got[3][-1].abs().max().item() == 0.0        # the unreferenced source
     lse = _read(os.path.join(d, "lse.bin"), torch.float32, (graph.n_rows, heads))
     assert lse[0].abs().max().item() == 0.0 and bool(torch.isfinite(lse).all())
+
+
+# The closed-form legs of rowtile_ref.py on the source (cut-down graph: rows of 0, 1, 7 .. 9, 63 .. 65, 255 .. 257 and 400 distinct
+# entries): 3 x 24 bf16 = 3 of 4 lanes a head, 12 of 16 lanes a row; 5 x 8 fp32 = 5 heads of 2 lanes in 16 (3 idle heads);
+# 33 x 8 fp32 = two column blocks of 32 heads of 2 lanes, the second with one head.
+@pytest.mark.parametrize("leg", ["flat", "onehot"])
+@pytest.mark.parametrize("heads,D,dtype,shared", [(3, 24, torch.bfloat16, True), (5, 8, torch.float32, False), (33, 8, torch.float32, False)],
+                         ids=lambda v: str(v).replace("torch.", ""))
+def test_closed_form_legs_in_lock_step(emulator, tmp_path, heads, D, dtype, shared, leg):
+    import rowtile_ref as R
+
+    graph = R.emu_graph()
+    case = R.Case(dtype, heads, D, None)
+    q, k, v, g, scale = R.attn_operands(graph, case, leg, shared)
+    F, d = heads * D, str(tmp_path)
+    gt, _ = graph.csr().transpose()
+    for name, t in (("rowptr", graph.rowptr), ("col", graph.col), ("trowptr", gt.rowptr), ("tcol", gt.col), ("q", q), ("k", k), ("v", v),
+                    ("g", g)):
+        _dump(t, os.path.join(d, name + ".bin"))
+    res = subprocess.run([emulator, d, str(graph.n_rows), str(graph.n_cols), str(heads), str(D), "0" if dtype == torch.float32 else "1",
+                          repr(scale), "1" if shared else "0"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0 and "emu ok" in res.stdout, res.stdout + res.stderr
+    got = {n: _read(os.path.join(d, n + ".bin"), dtype, (rows, F))
+           for n, rows in (("out", graph.n_rows), ("dq", graph.n_rows), ("dk", graph.n_cols), ("dv", graph.n_cols))}
+    lse = _read(os.path.join(d, "lse.bin"), torch.float32, (graph.n_rows, heads))
+    ref = R.attn_reference(graph, q, k, v, g, heads, scale)
+    empty = np.flatnonzero(graph.deg == 0)
+    bad = R.check_finite("out", got["out"]) + R.check_finite("lse", lse) + R.check_zero_rows("out", got["out"], empty) \
+        + R.check_zero_rows("lse", lse, empty)
+    if leg == "onehot":
+        win, mult, top = R.winners(graph, ref["s"])
+        want, keep = R.onehot_expected(graph, v, win, mult, heads)
+        assert bool(keep.all())
+        bad += R.check_equal("out", got["out"], want, keep, heads)
+        bad += R.check_lse("lse", lse, *R.onehot_lse(top, mult))[0]
+    else:
+        bad += R.check_flat_forward("out", got["out"], ref["mean"])[0]
+        bad += R.check_lse("lse", lse, ref["lse"], R.flat_lse_bar(graph, ref))[0]
+        for name in ("dq", "dk", "dv"):
+            found, frac = R.check_units(name, got[name], ref[name])
+            print("%s %dx%d %s: %.3f of the bar" % (leg, heads, D, name, frac))
+            bad += found + R.check_finite(name, got[name])
+        bad += R.check_zero_rows("dq", got["dq"], empty)
+        for name in ("dk", "dv"):
+            bad += R.check_zero_rows(name, got[name], graph.unreferenced)
+    assert not bad, "\n".join(bad)
