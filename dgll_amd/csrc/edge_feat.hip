@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void ef_forward_kernel(const Args a) {
         }
     };
 
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         const float s = a.scale ? a.scale[row] : 1.0f;
         float o[EPV];
@@ -99,21 +99,11 @@ __global__ __launch_bounds__(kBlock) void ef_forward_kernel(const Args a) {
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), o);       // a row without entries: zeros
     };
 
-    auto clear = [&] {
+    auto load_row = [&](int64_t, int64_t, int64_t, bool) {
 #pragma unroll
         for (int d = 0; d < EPV; ++d) acc[d] = 0.0f;
     };
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        clear();
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if (mine) finish(row);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        clear();
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        rt::merge_partials<false>(acc, lds, lanes, [&] { finish(row); });
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    rt::reduce_rows<false>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, acc, lds, load_row, batch, finish);
 }
 
 // ---- cols: rows of A^T ---------------------------------------------------------------------------------------------------------------
@@ -131,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void ef_cols_kernel(const Args a) {
 
     float acc[EPV], xj[EPV];
 
-    auto load_row = [&](int64_t row, bool on) {
+    auto load_row = [&](int64_t row, int64_t, int64_t, bool on) {
 #pragma unroll
         for (int d = 0; d < EPV; ++d) acc[d] = xj[d] = 0.0f;
         if constexpr (OP == DGLL_EF_ADD_RELU) {
@@ -187,22 +177,12 @@ __global__ __launch_bounds__(kBlock) void ef_cols_kernel(const Args a) {
         }
     };
 
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), acc);     // a source no row references: zeros
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if (mine) finish(row);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(row, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        rt::merge_partials<false>(acc, lds, lanes, [&] { finish(row); });
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    rt::reduce_rows<false>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, acc, lds, load_row, batch, finish);
 }
 
 // ---- edge: one row of grad_e per entry, no reduction ------------------------------------------------------------------------------------
@@ -219,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void ef_edge_kernel(const Args a) {
 
     float gi[EPV];                                          // s_i g[i]
 
-    auto load_row = [&](int64_t row, bool on) {
+    auto load_row = [&](int64_t row, int64_t, int64_t, bool on) {
         typename IO::raw_t r = IO::zero();
         float s = 1.0f;
         if (on && active) {
@@ -266,15 +246,8 @@ __global__ __launch_bounds__(kBlock) void ef_edge_kernel(const Args a) {
         }
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {           // every lane group holds g[i] and takes its share of the entries
-        load_row(row, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    // (a long row: every lane group holds g[i] and takes its share of the entries)
+    rt::sweep_rows(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, load_row, batch);
 }
 
 template <typename T, int OP>
@@ -296,31 +269,15 @@ void launch(int pass, int op, dim3 grid, hipStream_t s, const Args& a) {
 
 using namespace dgll;
 
-// one operand of `dtype`: each requirement under the field's own name
-#define DGLL_EF_MATRIX(field, ld_field)                                                                                              \
-    do {                                                                                                                             \
-        DGLL_REQUIRE(d->field != nullptr, "dgll_hip_edge_feat_pass: " #field " must be non-NULL for this pass and op");              \
-        DGLL_REQUIRE(aligned16(d->field), "dgll_hip_edge_feat_pass: " #field " must be 16-byte aligned");                            \
-        DGLL_REQUIRE(d->ld_field % epv == 0 && d->ld_field >= d->F,                                                                  \
-                     "dgll_hip_edge_feat_pass: " #ld_field " must be a pitch of whole 16-byte vectors >= F");                        \
-    } while (0)
-
 DGLL_API int dgll_hip_edge_feat_pass(void* stream, const dgll_edge_feat_desc* d) {
+    static const char* const kPass = "dgll_hip_edge_feat_pass";
     DGLL_REQUIRE(d != nullptr, "dgll_hip_edge_feat_pass: the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_EF_FORWARD || d->pass == DGLL_EF_COLS || d->pass == DGLL_EF_EDGE,
                  "dgll_hip_edge_feat_pass: pass must be DGLL_EF_FORWARD, DGLL_EF_COLS or DGLL_EF_EDGE");
     DGLL_REQUIRE(d->op == DGLL_EF_ADD || d->op == DGLL_EF_ADD_RELU || d->op == DGLL_EF_MUL,
                  "dgll_hip_edge_feat_pass: op must be DGLL_EF_ADD, DGLL_EF_ADD_RELU or DGLL_EF_MUL");
-    DGLL_REQUIRE(d->dtype == DGLL_F32 || d->dtype == DGLL_BF16, "dgll_hip_edge_feat_pass: dtype must be DGLL_F32 or DGLL_BF16");
-    const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-    DGLL_REQUIRE(d->F >= epv && d->F % epv == 0 && d->F < (1ll << 24),
-                 "dgll_hip_edge_feat_pass: F a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns), below 2^24");
-    DGLL_REQUIRE(d->n_rows >= 0 && d->n_rows < (1ll << 31) && d->n_cols > 0 && d->n_cols < (1ll << 31),
-                 "dgll_hip_edge_feat_pass: n_rows in [0, 2^31), n_cols (the gathered rows) in [1, 2^31)");
-    DGLL_REQUIRE(d->nnz >= 0 && d->nnz < (1ll << 31), "dgll_hip_edge_feat_pass: nnz (the rows of e and grad_e) in [0, 2^31)");
-    DGLL_REQUIRE(d->rowptr != nullptr, "dgll_hip_edge_feat_pass: the CSR array rowptr must be non-NULL");
-    DGLL_REQUIRE(d->col != nullptr, "dgll_hip_edge_feat_pass: the CSR array col must be non-NULL");
-    const int64_t esz = d->dtype == DGLL_F32 ? 4 : 2;
+    if (const int rc = rt::require_flat_pass(kPass, d->dtype, d->F, d->n_rows, d->n_cols, d->nnz, d->rowptr, d->col, true)) return rc;
+    const auto [epv, esz] = rt::storage_of(d->dtype);
     const bool relu = d->op == DGLL_EF_ADD_RELU, mul = d->op == DGLL_EF_MUL;
 
     ef::Args a{};
@@ -333,13 +290,13 @@ DGLL_API int dgll_hip_edge_feat_pass(void* stream, const dgll_edge_feat_desc* d)
     bool read_x, read_e;
     if (d->pass == DGLL_EF_FORWARD) {
         read_x = read_e = true;
-        DGLL_EF_MATRIX(out, ld_out);
+        DGLL_REQUIRE_OPERAND(kPass, out, d->F);
         a.out = static_cast<char*>(d->out);             a.pb_out = d->ld_out * esz;
     } else if (d->pass == DGLL_EF_COLS) {
         read_x = relu;
         read_e = relu || mul;
-        DGLL_EF_MATRIX(grad_out, ld_grad_out);
-        DGLL_EF_MATRIX(grad_x, ld_grad_x);
+        DGLL_REQUIRE_OPERAND(kPass, grad_out, d->F);
+        DGLL_REQUIRE_OPERAND(kPass, grad_x, d->F);
         DGLL_REQUIRE(!read_e || d->perm != nullptr, "dgll_hip_edge_feat_pass: cols: perm must be non-NULL when e is read (ADD_RELU, MUL)");
         a.perm = d->perm;
         a.g = static_cast<const char*>(d->grad_out);    a.pb_g = d->ld_grad_out * esz;
@@ -347,28 +304,25 @@ DGLL_API int dgll_hip_edge_feat_pass(void* stream, const dgll_edge_feat_desc* d)
     } else {
         read_x = relu || mul;
         read_e = relu;
-        DGLL_EF_MATRIX(grad_out, ld_grad_out);
-        DGLL_EF_MATRIX(grad_e, ld_grad_e);
+        DGLL_REQUIRE_OPERAND(kPass, grad_out, d->F);
+        DGLL_REQUIRE_OPERAND(kPass, grad_e, d->F);
         a.g = static_cast<const char*>(d->grad_out);    a.pb_g = d->ld_grad_out * esz;
         a.out = static_cast<char*>(d->grad_e);          a.pb_out = d->ld_grad_e * esz;
     }
     if (read_x) {
-        DGLL_EF_MATRIX(x, ld_x);
+        DGLL_REQUIRE_OPERAND(kPass, x, d->F);
         a.x = static_cast<const char*>(d->x);           a.pb_x = d->ld_x * esz;
     }
     if (read_e) {
-        DGLL_EF_MATRIX(e, ld_e);
+        DGLL_REQUIRE_OPERAND(kPass, e, d->F);
         a.e = static_cast<const char*>(d->e);           a.pb_e = d->ld_e * esz;
     }
-    const int64_t vpr = d->F / epv;
-    a.vpr = (int)vpr;
-    const rt::HeadGeometry geo = rt::make_row_geometry(rt::pow2_at_least(vpr < kWave ? vpr : kWave, rt::kMinGroup), d->n_rows);
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
+    a.vpr = (int)(d->F / epv);
+    const rt::HeadGeometry geo = rt::make_flat_geometry(a.vpr, d->n_rows);
+    rt::set_geometry(a, geo);
     if (geo.grid == 0) return DGLL_OK;
-    const int64_t chunks = (vpr + a.lpr - 1) / a.lpr;
-    DGLL_REQUIRE(chunks <= 65535, "dgll_hip_edge_feat_pass: F at most 64 * 65535 vectors");
-    const dim3 grid((unsigned)geo.grid, (unsigned)chunks);
+    dim3 grid;
+    if (const int rc = rt::launch_grid(kPass, geo.grid, geo.col_blocks, 1, grid)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->dtype == DGLL_F32) ef::launch<float>(d->pass, d->op, grid, st, a);
     else ef::launch<bf16_t>(d->pass, d->op, grid, st, a);

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_kernel(const Args a) {
 #pragma unroll
     for (int d = 0; d < (KIND == 1 ? EPV : 1); ++d) dacc[d] = 0.0f;
 
-    auto load_row = [&](int64_t row, bool on) {
+    auto load_row = [&](int64_t row, int64_t, int64_t, bool on) {
         const bool ld = on && active;
         typename IO::raw_t r = IO::zero();
         if (ld) r = IO::load(reinterpret_cast<const T*>((KIND == 2 ? a.xl : a.xr) + row * (KIND == 2 ? a.pb_xl : a.pb_xr) + cb));
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_kernel(const Args a) {
     };
 
     // the row's outputs from its complete state; no cross-lane traffic (the long-row path calls it from one lane group alone)
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         float o[EPV];
         if constexpr (KIND == 0) {
@@ -205,17 +205,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_kernel(const Args a) {
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), o);
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if (mine) finish(row);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(row, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        rt::merge_partials<KIND == 0>(st, lds, lanes, [&] { finish(row); });
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    rt::reduce_rows<KIND == 0>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, st, lds, load_row, batch, finish);
 
     if constexpr (KIND == 1) {                  // this workgroup's dattn partial: its lane groups' shares in group order
         const int tid = lanes.tid;
@@ -257,21 +247,21 @@ void launch(int pass, dim3 grid, hipStream_t s, const Args& a) {
 using namespace dgll;
 
 DGLL_API int dgll_hip_gatv2_pass(void* stream, const dgll_gatv2_desc* d) {
+    static const char* const kPass = "dgll_hip_gatv2_pass";
     DGLL_REQUIRE(d != nullptr, "the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_GATV2_FORWARD || d->pass == DGLL_GATV2_ROWS || d->pass == DGLL_GATV2_TRANSPOSED,
                  "pass must be DGLL_GATV2_FORWARD, DGLL_GATV2_ROWS or DGLL_GATV2_TRANSPOSED");
     if (const int rc = rt::require_head_pass(d->dtype, d->heads, d->D, d->n_rows, d->n_cols, d->rowptr, d->col)) return rc;
-    const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-    DGLL_REQUIRE(d->xl && d->xr && d->attn && d->out, "xl, xr, attn and the pass's output matrix must be non-NULL");
+    const auto [epv, esz] = rt::storage_of(d->dtype);
     const int64_t feat = (int64_t)d->heads * d->D;
-    DGLL_REQUIRE(rt::require_matrix(d->xl, d->ld_xl, epv, feat) && rt::require_matrix(d->xr, d->ld_xr, epv, feat) &&
-                     rt::require_matrix(d->out, d->ld_out, epv, feat),
-                 "xl, xr and the output: 16-byte aligned base, a pitch of whole 16-byte vectors >= heads * D");
+    DGLL_REQUIRE_OPERAND(kPass, xl, d->heads * d->D);
+    DGLL_REQUIRE_OPERAND(kPass, xr, d->heads * d->D);
+    DGLL_REQUIRE_OPERAND(kPass, out, d->heads * d->D);
+    DGLL_REQUIRE(d->attn != nullptr, "attn must be non-NULL");
     if (d->pass == DGLL_GATV2_FORWARD) {
         DGLL_REQUIRE(d->lse != nullptr, "forward: lse must be non-NULL");
     } else {
-        DGLL_REQUIRE(rt::require_matrix(d->grad_out, d->ld_grad_out, epv, feat),
-                     "backward: grad_out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+        DGLL_REQUIRE_OPERAND(kPass, grad_out, d->heads * d->D);
         DGLL_REQUIRE(d->lse_delta != nullptr, "backward: lse_delta must be non-NULL");
         if (d->pass == DGLL_GATV2_ROWS)
             DGLL_REQUIRE(d->lse && d->dattn_part && d->dattn_blocks >= 1 && d->dattn_blocks <= rt::kMaxGridX,
@@ -283,8 +273,7 @@ DGLL_API int dgll_hip_gatv2_pass(void* stream, const dgll_gatv2_desc* d) {
     a.col = d->col;
     a.n_rows = d->n_rows;
     a.n_cols = d->n_cols;
-    const int64_t esz = d->dtype == DGLL_F32 ? 4 : 2;
-    a.xl = static_cast<const char*>(d->xl);       a.pb_xl = d->ld_xl * esz;
+    a.xl =static_cast<const char*>(d->xl);       a.pb_xl = d->ld_xl * esz;
     a.xr = static_cast<const char*>(d->xr);       a.pb_xr = d->ld_xr * esz;
     a.g = static_cast<const char*>(d->grad_out);  a.pb_g = d->ld_grad_out * esz;
     a.out = static_cast<char*>(d->out);           a.pb_out = d->ld_out * esz;
@@ -296,15 +285,11 @@ DGLL_API int dgll_hip_gatv2_pass(void* stream, const dgll_gatv2_desc* d) {
     a.D = d->D;
     a.slope = d->slope;
     const rt::HeadGeometry geo = rt::make_head_geometry(d->heads, d->D, epv, d->n_rows);
-    a.vph = geo.vph;
-    a.lph = geo.lph;
-    a.hpb = geo.hpb;
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
+    rt::set_geometry(a, geo);
     const int64_t gx = d->pass == DGLL_GATV2_ROWS ? d->dattn_blocks : geo.grid;    // every partial row is written, by a workgroup without tiles as zeros
     if (gx == 0) return DGLL_OK;
-    DGLL_REQUIRE(geo.col_blocks <= 65535, "at most 65535 column blocks of whole heads");
-    const dim3 grid((unsigned)gx, (unsigned)geo.col_blocks);
+    dim3 grid;
+    if (const int rc = rt::launch_grid(kPass, gx, geo.col_blocks, 1, grid)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->dtype == DGLL_F32) gv2::launch<float>(d->pass, grid, st, a);
     else gv2::launch<bf16_t>(d->pass, grid, st, a);

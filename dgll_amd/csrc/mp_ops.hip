@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kBlock) void mp_node_kernel(const Args a) {
 
     float st[EPV];
 
-    auto load_row = [&](int64_t row, bool on) {
+    auto load_row = [&](int64_t row, int64_t, int64_t, bool on) {
         typename IO::raw_t r = IO::zero();
         if constexpr (KIND == 1) {
             if (on && active) r = IO::load(reinterpret_cast<const T*>(a.y + row * a.pb_y + cb));
@@ -324,24 +324,26 @@ __global__ __launch_bounds__(kBlock) void mp_node_kernel(const Args a) {
     };
 
     // the row's output from its complete state; no cross-lane traffic (the long-row path calls it from one lane group alone)
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), st);      // an empty row: zeros
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if constexpr (KIND == 0) {
-            if (mine) finish(row);
-        }
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(row, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        if constexpr (KIND == 0) rt::merge_partials<false>(st, lds, lanes, [&] { finish(row); });   // (dots: every entry is already stored)
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    if constexpr (KIND == 0) {
+        rt::reduce_rows<false>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, st, lds, load_row, batch, finish);
+    } else {
+        // dots: every entry is already stored.  rt::sweep_rows written out: through the header one instruction of this kernel moves
+        // (a refactor does not change instruction text).
+        auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
+            load_row(row, b, e, mine);
+            rt::for_each_batch(b, e, 0, 1, lanes, batch);
+        };
+        auto long_row = [&](int64_t row, int64_t b, int64_t e) {
+            load_row(row, b, e, true);
+            rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
+        };
+        rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    }
 }
 
 template <int KIND>
@@ -366,6 +368,7 @@ void launch_node(int pass, dim3 grid, hipStream_t s, const Args& a) {
 using namespace dgll;
 
 DGLL_API int dgll_hip_mp_pass(void* stream, const dgll_mp_desc* d) {
+    static const char* const kPass = "dgll_hip_mp_pass";
     DGLL_REQUIRE(d != nullptr, "dgll_hip_mp_pass: the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass >= DGLL_MP_EDGE_SOFTMAX && d->pass <= DGLL_MP_U_DOT_V,
                  "dgll_hip_mp_pass: pass must be one of DGLL_MP_EDGE_SOFTMAX .. DGLL_MP_U_DOT_V");
@@ -389,31 +392,23 @@ DGLL_API int dgll_hip_mp_pass(void* stream, const dgll_mp_desc* d) {
 
     if (node) {
         if (const int rc = rt::require_head_pass(d->dtype, d->heads, d->D, d->n_rows, d->n_cols, d->rowptr, d->col)) return rc;
-        const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-        const int64_t feat = (int64_t)d->heads * d->D, esz = d->dtype == DGLL_F32 ? 4 : 2;
-        DGLL_REQUIRE(rt::require_matrix(d->x, d->ld_x, epv, feat),
-                     "dgll_hip_mp_pass: x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+        const auto [epv, esz] = rt::storage_of(d->dtype);
+        DGLL_REQUIRE_OPERAND(kPass, x, d->heads * d->D);
         if (d->pass == DGLL_MP_U_MUL_E_SUM) {
             DGLL_REQUIRE(edge_array(d->e, d->ld_e), "dgll_hip_mp_pass: u_mul_e_sum: e non-NULL with a pitch >= heads");
-            DGLL_REQUIRE(rt::require_matrix(d->out, d->ld_out, epv, feat),
-                         "dgll_hip_mp_pass: u_mul_e_sum: out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+            DGLL_REQUIRE_OPERAND(kPass, out, d->heads * d->D);
         } else {
-            DGLL_REQUIRE(rt::require_matrix(d->y, d->ld_y, epv, feat),
-                         "dgll_hip_mp_pass: u_dot_v: y non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+            DGLL_REQUIRE_OPERAND(kPass, y, d->heads * d->D);
             DGLL_REQUIRE(edge_array(d->e_out, d->ld_e_out), "dgll_hip_mp_pass: u_dot_v: e_out non-NULL with a pitch >= heads");
         }
         a.x = static_cast<const char*>(d->x);      a.pb_x = d->ld_x * esz;
         a.y = static_cast<const char*>(d->y);      a.pb_y = d->ld_y * esz;
         a.out = static_cast<char*>(d->out);        a.pb_out = d->ld_out * esz;
         const rt::HeadGeometry geo = rt::make_head_geometry(d->heads, d->D, epv, d->n_rows);
-        a.vph = geo.vph;
-        a.lph = geo.lph;
-        a.hpb = geo.hpb;
-        a.lpr = geo.lpr;
-        a.tiles = geo.tiles;
+        rt::set_geometry(a, geo);
         if (geo.grid == 0 || (d->nnz == 0 && d->pass == DGLL_MP_U_DOT_V)) return DGLL_OK;
-        DGLL_REQUIRE(geo.col_blocks <= 65535, "dgll_hip_mp_pass: at most 65535 column blocks of whole heads");
-        const dim3 grid((unsigned)geo.grid, (unsigned)geo.col_blocks);
+        dim3 grid;
+        if (const int rc = rt::launch_grid(kPass, geo.grid, geo.col_blocks, 1, grid)) return rc;
         if (d->dtype == DGLL_F32) mp::launch_node<float>(d->pass, grid, st, a);
         else mp::launch_node<bf16_t>(d->pass, grid, st, a);
         DGLL_HIP_TRY(hipGetLastError());
@@ -447,10 +442,8 @@ DGLL_API int dgll_hip_mp_pass(void* stream, const dgll_mp_desc* d) {
             DGLL_REQUIRE(edge_array(d->e_out, d->ld_e_out), "dgll_hip_mp_pass: edge_softmax: e_out non-NULL with a pitch >= heads");
         }
     }
-    a.vph = a.lph = a.hpb = 0;
-    const rt::HeadGeometry geo = rt::make_row_geometry(mp::kEdgeLanes, d->n_rows);
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
+    const rt::HeadGeometry geo = rt::make_row_geometry(mp::kEdgeLanes, d->n_rows);      // (no heads in the lanes: vph = lph = hpb = 0)
+    rt::set_geometry(a, geo);
     if (geo.grid == 0 || (d->nnz == 0 && d->pass != DGLL_MP_E_SUM)) return DGLL_OK;
     int hb = 1;
     while (hb < mp::kHeadBlock && hb < d->heads) hb <<= 1;

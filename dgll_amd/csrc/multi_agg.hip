@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void magg_forward_kernel(const Args a) {
     float sh[EPV], s1[EPV], s2[EPV], mx[EPV], mn[EPV];      // shift; sum and sum of squares about it; maximum, minimum
     int amx[EPV], amn[EPV];                                 // the source rows attaining them
 
-    auto load_row = [&](int64_t b, int64_t e, bool on) {
+    auto load_row = [&](int64_t, int64_t b, int64_t e, bool on) {
 #pragma unroll
         for (int d = 0; d < EPV; ++d) {
             s1[d] = s2[d] = 0.0f;
@@ -220,13 +220,15 @@ __global__ __launch_bounds__(kBlock) void magg_forward_kernel(const Args a) {
         __syncthreads();
     };
 
+    // rt::sweep_rows written out: through the header the fp32 kernel's registers are numbered differently (a refactor does
+    // not change instruction text).  A long row: the first lane group takes the others' sums, then maxima, then minima, and writes it.
     auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(b, e, mine);
+        load_row(row, b, e, mine);
         rt::for_each_batch(b, e, 0, 1, lanes, batch);
         if (mine) finish(row, b, e);
     };
     auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(b, e, true);
+        load_row(row, b, e, true);
         rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
         float bits[EPV];
         exchange(s1, s2);
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void magg_cols_kernel(const Args a) {
     int64_t row_b = 0;                                      // the current row and its first entry
     int cur = 0;
 
-    auto load_row = [&](int64_t row, int64_t b, bool on) {
+    auto load_row = [&](int64_t row, int64_t b, int64_t, bool on) {
         row_b = b;
         cur = (int)row;
 #pragma unroll
@@ -398,22 +400,12 @@ __global__ __launch_bounds__(kBlock) void magg_cols_kernel(const Args a) {
         }
     };
 
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), acc);     // a source no row references: zeros
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, b, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if (mine) finish(row);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(row, b, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        rt::merge_partials<false>(acc, lds, lanes, [&] { finish(row); });
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    rt::reduce_rows<false>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, acc, lds, load_row, batch, finish);
 }
 
 template <typename T>
@@ -432,17 +424,13 @@ inline bool side_array(const void* p, int64_t ld, int64_t blocks, int64_t F) { r
 using namespace dgll;
 
 DGLL_API int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d) {
+    static const char* const kPass = "dgll_hip_multi_agg_pass";
     DGLL_REQUIRE(d != nullptr, "dgll_hip_multi_agg_pass: the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_MAGG_FORWARD || d->pass == DGLL_MAGG_ROWS || d->pass == DGLL_MAGG_COLS,
                  "dgll_hip_multi_agg_pass: pass must be DGLL_MAGG_FORWARD, DGLL_MAGG_ROWS or DGLL_MAGG_COLS");
-    DGLL_REQUIRE(d->dtype == DGLL_F32 || d->dtype == DGLL_BF16, "dgll_hip_multi_agg_pass: dtype must be DGLL_F32 or DGLL_BF16");
-    const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-    DGLL_REQUIRE(d->F >= epv && d->F % epv == 0 && d->F < (1ll << 24),
-                 "dgll_hip_multi_agg_pass: F a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns), below 2^24");
-    DGLL_REQUIRE(d->n_rows >= 0 && d->n_rows < (1ll << 31) && d->n_cols > 0 && d->n_cols < (1ll << 31),
-                 "dgll_hip_multi_agg_pass: row count in [0, 2^31), gathered row count in [1, 2^31)");
     const bool fwd = d->pass == DGLL_MAGG_FORWARD, rows = d->pass == DGLL_MAGG_ROWS;
-    DGLL_REQUIRE(d->rowptr && (rows || d->col), "dgll_hip_multi_agg_pass: the CSR arrays rowptr and col must be non-NULL (rows: rowptr)");
+    if (const int rc = rt::require_flat_pass(kPass, d->dtype, d->F, d->n_rows, d->n_cols, 0, d->rowptr, d->col, !rows)) return rc;
+    const auto [epv, esz] = rt::storage_of(d->dtype);
     DGLL_REQUIRE(d->n_agg >= 1 && d->n_agg <= 6, "dgll_hip_multi_agg_pass: n_agg in [1, 6]");
     DGLL_REQUIRE(d->n_scaler >= 1 && d->n_scaler <= 3, "dgll_hip_multi_agg_pass: n_scaler in [1, 3]");
     uint32_t aggs = 0, scalers = 0;
@@ -466,7 +454,6 @@ DGLL_API int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d)
         scalers |= (uint32_t)c << (4 * i);
     }
     DGLL_REQUIRE(d->delta > 0.0f && d->delta < INFINITY, "dgll_hip_multi_agg_pass: delta must be a positive finite number");
-    const int64_t wide = (int64_t)d->n_agg * d->n_scaler * d->F, esz = d->dtype == DGLL_F32 ? 4 : 2;
     const bool need_var = need & magg::kNeedVar, need_arg = need & (magg::kNeedMax | magg::kNeedMin);
 
     magg::Args a{};
@@ -483,12 +470,9 @@ DGLL_API int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d)
     a.need = need;
     a.delta = d->delta;
     if (fwd) {
-        DGLL_REQUIRE(rt::require_matrix(d->x, d->ld_x, epv, d->F),
-                     "dgll_hip_multi_agg_pass: forward: x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= F");
-        DGLL_REQUIRE(!d->y || rt::require_matrix(d->y, d->ld_y, epv, d->F),
-                     "dgll_hip_multi_agg_pass: forward: y, where given, 16-byte aligned on a pitch of whole 16-byte vectors >= F");
-        DGLL_REQUIRE(rt::require_matrix(d->out, d->ld_out, epv, wide),
-                     "dgll_hip_multi_agg_pass: forward: out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= n_scaler * n_agg * F");
+        DGLL_REQUIRE_OPERAND(kPass, x, d->F);
+        if (d->y) DGLL_REQUIRE_OPERAND(kPass, y, d->F);
+        DGLL_REQUIRE_OPERAND(kPass, out, d->n_scaler * d->n_agg * d->F);
         DGLL_REQUIRE(!d->stats || magg::side_array(d->stats, d->ld_stats, 2, d->F),
                      "dgll_hip_multi_agg_pass: forward: stats, where given, 16-byte aligned fp32 on a pitch of whole vectors >= 2 F");
         DGLL_REQUIRE(!d->arg || magg::side_array(d->arg, d->ld_arg, 2, d->F),
@@ -499,43 +483,36 @@ DGLL_API int dgll_hip_multi_agg_pass(void* stream, const dgll_multi_agg_desc* d)
         a.stats = d->stats;                         a.ld_stats = d->ld_stats;
         a.arg = d->arg;                             a.ld_arg = d->ld_arg;
     } else if (rows) {
-        DGLL_REQUIRE(rt::require_matrix(d->grad_out, d->ld_grad_out, epv, wide),
-                     "dgll_hip_multi_agg_pass: rows: grad_out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= n_scaler * n_agg * F");
+        DGLL_REQUIRE_OPERAND(kPass, grad_out, d->n_scaler * d->n_agg * d->F);
         DGLL_REQUIRE(d->coef || d->grad_y, "dgll_hip_multi_agg_pass: rows: one of coef and grad_y must be given");
         DGLL_REQUIRE(!d->coef || magg::side_array(d->coef, d->ld_coef, magg::kCoefBlocks, d->F),
                      "dgll_hip_multi_agg_pass: rows: coef, where given, 16-byte aligned fp32 on a pitch of whole vectors >= 5 F");
         DGLL_REQUIRE(!(d->coef && need_var) || d->stats, "dgll_hip_multi_agg_pass: rows: stats must be non-NULL when VAR or STD is asked");
         DGLL_REQUIRE(!d->stats || magg::side_array(d->stats, d->ld_stats, 2, d->F),
                      "dgll_hip_multi_agg_pass: rows: stats 16-byte aligned fp32 on a pitch of whole vectors >= 2 F");
-        DGLL_REQUIRE(!d->grad_y || rt::require_matrix(d->grad_y, d->ld_grad_y, epv, d->F),
-                     "dgll_hip_multi_agg_pass: rows: grad_y, where given, 16-byte aligned on a pitch of whole 16-byte vectors >= F");
+        if (d->grad_y) DGLL_REQUIRE_OPERAND(kPass, grad_y, d->F);
         a.g = static_cast<const char*>(d->grad_out);    a.pb_g = d->ld_grad_out * esz;
         a.stats = d->stats;                             a.ld_stats = d->ld_stats;
         a.coef = d->coef;                               a.ld_coef = d->ld_coef;
         a.out = static_cast<char*>(d->grad_y);          a.pb_out = d->ld_grad_y * esz;
     } else {
-        DGLL_REQUIRE(rt::require_matrix(d->x, d->ld_x, epv, d->F),
-                     "dgll_hip_multi_agg_pass: cols: x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= F");
+        DGLL_REQUIRE_OPERAND(kPass, x, d->F);
         DGLL_REQUIRE(magg::side_array(d->coef, d->ld_coef, magg::kCoefBlocks, d->F),
                      "dgll_hip_multi_agg_pass: cols: coef non-NULL, 16-byte aligned fp32 on a pitch of whole vectors >= 5 F");
         DGLL_REQUIRE(!need_arg || magg::side_array(d->arg, d->ld_arg, 2, d->F),
                      "dgll_hip_multi_agg_pass: cols: arg non-NULL (MAX or MIN is asked), 16-byte aligned int32 on a pitch of whole vectors >= 2 F");
-        DGLL_REQUIRE(rt::require_matrix(d->grad_x, d->ld_grad_x, epv, d->F),
-                     "dgll_hip_multi_agg_pass: cols: grad_x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= F");
+        DGLL_REQUIRE_OPERAND(kPass, grad_x, d->F);
         a.x = static_cast<const char*>(d->x);           a.pb_x = d->ld_x * esz;
         a.coef = d->coef;                               a.ld_coef = d->ld_coef;
         a.arg = d->arg;                                 a.ld_arg = d->ld_arg;
         a.out = static_cast<char*>(d->grad_x);          a.pb_out = d->ld_grad_x * esz;
     }
-    const int64_t vpr = d->F / epv;
-    a.vpr = (int)vpr;
-    const rt::HeadGeometry geo = rt::make_row_geometry(rt::pow2_at_least(vpr < kWave ? vpr : kWave, rt::kMinGroup), d->n_rows);
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
+    a.vpr = (int)(d->F / epv);
+    const rt::HeadGeometry geo = rt::make_flat_geometry(a.vpr, d->n_rows);
+    rt::set_geometry(a, geo);
     if (geo.grid == 0) return DGLL_OK;
-    const int64_t chunks = (vpr + a.lpr - 1) / a.lpr;
-    DGLL_REQUIRE(chunks <= 65535, "dgll_hip_multi_agg_pass: F at most 64 * 65535 vectors");
-    const dim3 grid((unsigned)geo.grid, (unsigned)chunks);
+    dim3 grid;
+    if (const int rc = rt::launch_grid(kPass, geo.grid, geo.col_blocks, 1, grid)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->dtype == DGLL_F32) magg::launch<float>(d->pass, grid, st, a);
     else magg::launch<bf16_t>(d->pass, grid, st, a);

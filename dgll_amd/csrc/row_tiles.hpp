@@ -1,6 +1,14 @@
-// row_tiles.hpp -- the row-tile skeleton of the gather passes that keep a flat per-lane state: gatv2.hip, sparse_attn.hip, typed_spmm.hip.
-// Each of them supplies its own math (load a row, add one entry, finish a row); the rest is here, once -- but for the batch loop, the
-// tile loop and the sliced merge of typed_spmm.hip, which that file writes out (it says why).
+// row_tiles.hpp -- the row-tile skeleton of the gather passes that keep a flat per-lane state: gatv2.hip, sparse_attn.hip, typed_spmm.hip,
+// mp_ops.hip, multi_agg.hip, edge_feat.hip.  Each of them supplies its own math (load a row, add one batch of entries, finish a row);
+// the rest is here, once: on the device the lanes, the batch and tile loops, the long-row merge and the row sweep that ties them
+// together (sweep_rows / reduce_rows); on the host the prologue of a descriptor entry point (storage_of, require_head_pass /
+// require_flat_pass, DGLL_REQUIRE_OPERAND, make_head_geometry / make_flat_geometry, set_geometry, launch_grid).  What a file still
+// writes out, because through the header its instruction text changes (each says so at the place):
+//   typed_spmm.hip   the batch loop, the tile loop with the chunk loop inside, and the sliced merge
+//   mp_ops.hip       mp_edge_kernel: the head-block loop sits outside its two sweeps of a row; mp_node_kernel<*, 1> (dots): the row sweep
+//   multi_agg.hip    magg_forward_kernel: the row sweep (its long-row end is three LDS exchanges of its own)
+// and, in every kernel, the few lines that decode the lane's columns (hl / v / head / active / cb): as a shared helper they moved
+// register counts.
 //
 // Lane layout: a lane owns one 16-byte vector of columns, a row `lpr` adjacent lanes (a power of two >= 8; the lanes past the row's
 // vectors idle), a wavefront 64 / lpr rows at a time.  A workgroup takes tiles of `groups` = 4 * 64 / lpr consecutive rows, grid-stride:
@@ -9,6 +17,9 @@
 // k + groups, ... and the partial states are merged through LDS in group order by the first group.  No atomics: two runs give the
 // same bits.  The attention passes put `hpb` whole heads of `lph` lanes each into a row's lanes (HeadGeometry).
 #pragma once
+#include <string>
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace dgll {
@@ -124,7 +135,50 @@ __device__ __forceinline__ void merge_partials(float (&st)[NP], float* lds, cons
     }
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------------------
+// The row sweep a gather kernel ends with.  begin(row, b, e, on) sets up the lane's state for a row (!on: no such row for this lane
+// group -- row = 0, b == e -- so it loads nothing); batch(k0, nb) adds one index batch; short_done(row, b, e) ends a row of at most
+// `longer_than` entries, in the lane group that swept it; long_done(row, b, e) ends a longer one, in every lane of the workgroup, each
+// lane group holding the partial state of its share of the batches.
+template <typename Begin, typename Batch, typename ShortDone, typename LongDone>
+__device__ __forceinline__ void sweep_rows(int64_t tiles, int64_t n_rows, const int64_t* rowptr, int longer_than, const Lanes& L,
+                                           Begin&& begin, Batch&& batch, ShortDone&& short_done, LongDone&& long_done) {
+    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
+        begin(row, b, e, mine);
+        for_each_batch(b, e, 0, 1, L, batch);
+        if (mine) short_done(row, b, e);
+    };
+    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
+        begin(row, b, e, true);
+        for_each_batch(b, e, L.gid, L.groups, L, batch);
+        long_done(row, b, e);
+    };
+    for_each_tile(tiles, n_rows, rowptr, longer_than, L, short_row, long_row);
+}
+
+// ... of a pass that leaves nothing to do at the end of a row (every entry's result is stored by its batch)
+template <typename Begin, typename Batch>
+__device__ __forceinline__ void sweep_rows(int64_t tiles, int64_t n_rows, const int64_t* rowptr, int longer_than, const Lanes& L,
+                                           Begin&& begin, Batch&& batch) {
+    auto nothing = [](int64_t, int64_t, int64_t) {};
+    sweep_rows(tiles, n_rows, rowptr, longer_than, L, begin, batch, nothing, nothing);
+}
+
+// ... of a pass that reduces a row into the flat state st: finish(row, b, e) writes the row from its complete state, after
+// merge_partials for a long row.
+template <bool SOFTMAX, int NP, typename Begin, typename Batch, typename Finish>
+__device__ __forceinline__ void reduce_rows(int64_t tiles, int64_t n_rows, const int64_t* rowptr, int longer_than, const Lanes& L,
+                                            float (&st)[NP], float* lds, Begin&& begin, Batch&& batch, Finish&& finish) {
+    auto long_done = [&](int64_t row, int64_t b, int64_t e) { merge_partials<SOFTMAX>(st, lds, L, [&] { finish(row, b, e); }); };
+    sweep_rows(tiles, n_rows, rowptr, longer_than, L, begin, batch, finish, long_done);
+}
+
+// ---- host side: the prologue of a descriptor entry point -----------------------------------------------------------------------
+struct Storage {
+    int epv;                                    // elements of a 16-byte lane vector
+    int64_t esz;                                // bytes of an element
+};
+inline Storage storage_of(int dtype) { return dtype == DGLL_F32 ? Storage{4, 4} : Storage{8, 2}; }
+
 struct HeadGeometry {
     int vph, lph, hpb, col_blocks;              // vectors and lanes of a head; whole heads per column block, and how many of those
     int lpr;                                    // lanes of a row
@@ -155,18 +209,75 @@ inline HeadGeometry make_head_geometry(int heads, int D, int epv, int64_t n_rows
     return g;
 }
 
-// a matrix of 16-byte lane vectors: non-NULL, 16-byte aligned base, a pitch of whole 16-byte vectors >= width
-inline bool require_matrix(const void* p, int64_t ld, int epv, int64_t width) { return p && aligned16(p) && ld % epv == 0 && ld >= width; }
+// The passes whose rows are F columns without heads (vpr = F / epv vectors): a row's lanes are the smallest power of two that holds
+// its vectors, 64 at the most, and wider rows are cut into column blocks of 64 vectors.
+inline HeadGeometry make_flat_geometry(int64_t vpr, int64_t n_rows) {
+    HeadGeometry g = make_row_geometry(pow2_at_least(vpr < kWave ? vpr : kWave, kMinGroup), n_rows);
+    g.col_blocks = (int)((vpr + g.lpr - 1) / g.lpr);
+    return g;
+}
+
+// the geometry into a kernel's Args: lpr and tiles, and the head fields where the Args have them
+template <typename A, typename = void> struct has_heads : std::false_type {};
+template <typename A> struct has_heads<A, std::void_t<decltype(A::lph)>> : std::true_type {};
+template <typename A>
+inline void set_geometry(A& a, const HeadGeometry& g) {
+    a.lpr = g.lpr;
+    a.tiles = g.tiles;
+    if constexpr (has_heads<A>::value) {
+        a.vph = g.vph;
+        a.lph = g.lph;
+        a.hpb = g.hpb;
+    }
+}
+
+// gridDim of the launch: gx workgroups (the geometry's grid, or the pass's own count) by gy column blocks by gz
+inline int launch_grid(const char* pass, int64_t gx, int64_t gy, int64_t gz, dim3& grid) {
+    DGLL_REQUIRE(gy <= 65535 && gz <= 65535, std::string(pass) + ": at most 65535 column blocks (of 64 lane vectors or of whole heads) and 65535 basis blocks");
+    grid = dim3((unsigned)gx, (unsigned)gy, (unsigned)gz);
+    return DGLL_OK;
+}
+
+// One matrix operand of 16-byte lane vectors, refused under its own name: non-NULL, a 16-byte aligned base, a pitch of whole 16-byte
+// vectors >= width (`width_is`: the width in the descriptor's terms).  Use through DGLL_REQUIRE_OPERAND.
+inline int require_operand(const char* pass, const char* name, const void* p, int64_t ld, int epv, int64_t width, const char* width_is) {
+    const std::string what = std::string(pass) + ": " + name + " non-NULL, 16-byte aligned, pitch ld_" + name + " of whole 16-byte vectors >= " + width_is + ": ";
+    DGLL_REQUIRE(p != nullptr, what + name + " must be non-NULL for this pass");
+    DGLL_REQUIRE(aligned16(p), what + name + " must be 16-byte aligned");
+    DGLL_REQUIRE(ld % epv == 0 && ld >= width, what + "ld_" + name + " is no such pitch");
+    return DGLL_OK;
+}
+// operand `field` of the descriptor d, on the pitch d->ld_<field>; `epv` is the caller's
+#define DGLL_REQUIRE_OPERAND(pass, field, width)                                                                        \
+    do {                                                                                                                \
+        if (const int rc_ = ::dgll::rt::require_operand(pass, #field, d->field, d->ld_##field, epv, width, #width)) return rc_; \
+    } while (0)
 
 // what every pass over heads requires of its descriptor's dtype, shape and CSR
 inline int require_head_pass(int dtype, int heads, int D, int64_t n_rows, int64_t n_cols, const void* rowptr, const void* col) {
     DGLL_REQUIRE(dtype == DGLL_F32 || dtype == DGLL_BF16, "dtype must be DGLL_F32 or DGLL_BF16");
-    const int epv = dtype == DGLL_F32 ? 4 : 8;
+    const int epv = storage_of(dtype).epv;
     DGLL_REQUIRE(heads >= 1 && D >= epv && D % epv == 0, "heads >= 1 and D a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns)");
     DGLL_REQUIRE(D / epv <= kWave, "a head may span at most 64 vectors (D <= 256 fp32, 512 bf16)");
     DGLL_REQUIRE((int64_t)heads * D < (1 << 20), "heads * D < 2^20");
     DGLL_REQUIRE(n_rows >= 0 && n_rows < (1ll << 31) && n_cols > 0 && n_cols < (1ll << 31), "row count in [0, 2^31), gathered row count in [1, 2^31)");
     DGLL_REQUIRE(rowptr && col, "the CSR arrays must be non-NULL");
+    return DGLL_OK;
+}
+
+// ... and every pass over rows of F columns; nnz: the rows of its per-edge matrices (0 where it has none); col may be NULL in a pass
+// that gathers nothing (!gathers)
+inline int require_flat_pass(const char* pass, int dtype, int64_t F, int64_t n_rows, int64_t n_cols, int64_t nnz, const void* rowptr,
+                             const void* col, bool gathers) {
+    const std::string at = std::string(pass) + ": ";
+    DGLL_REQUIRE(dtype == DGLL_F32 || dtype == DGLL_BF16, at + "dtype must be DGLL_F32 or DGLL_BF16");
+    const int epv = storage_of(dtype).epv;
+    DGLL_REQUIRE(F >= epv && F % epv == 0 && F < (1ll << 24), at + "F a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns), below 2^24");
+    DGLL_REQUIRE(n_rows >= 0 && n_rows < (1ll << 31) && n_cols > 0 && n_cols < (1ll << 31),
+                 at + "n_rows in [0, 2^31), n_cols (the gathered rows) in [1, 2^31)");
+    DGLL_REQUIRE(nnz >= 0 && nnz < (1ll << 31), at + "nnz (the rows of the per-edge matrices) in [0, 2^31)");
+    DGLL_REQUIRE(rowptr != nullptr, at + "the CSR array rowptr must be non-NULL");
+    DGLL_REQUIRE(col != nullptr || !gathers, at + "the CSR array col must be non-NULL");
     return DGLL_OK;
 }
 

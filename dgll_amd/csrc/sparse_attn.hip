@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
     float own[EPV], held[EPV], lse_i = 0.0f, nl = 0.0f;
     float st[NP];
 
-    auto load_row = [&](int64_t row, bool on) {
+    auto load_row = [&](int64_t row, int64_t, int64_t, bool on) {
         const bool ld = on && active;
         typename IO::raw_t r = IO::zero();
         if (ld) r = IO::load(reinterpret_cast<const T*>((KIND == 2 ? a.k : a.q) + row * (KIND == 2 ? a.pb_k : a.pb_q) + cb));
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
     };
 
     // the row's outputs from its complete state; no cross-lane traffic (the long-row path calls it from one lane group alone)
-    auto finish = [&](int64_t row) {
+    auto finish = [&](int64_t row, int64_t, int64_t) {
         if (!active) return;
         float o[EPV];
         if constexpr (KIND == 0) {
@@ -205,17 +205,7 @@ __global__ __launch_bounds__(kBlock) void sparse_attn_kernel(const Args a) {
         IO::store(reinterpret_cast<T*>(a.out + row * a.pb_out + cb), o);
     };
 
-    auto short_row = [&](int64_t row, bool mine, int64_t b, int64_t e) {
-        load_row(row, mine);
-        rt::for_each_batch(b, e, 0, 1, lanes, batch);
-        if (mine) finish(row);
-    };
-    auto long_row = [&](int64_t row, int64_t b, int64_t e) {
-        load_row(row, true);
-        rt::for_each_batch(b, e, lanes.gid, lanes.groups, lanes, batch);
-        rt::merge_partials<KIND == 0>(st, lds, lanes, [&] { finish(row); });
-    };
-    rt::for_each_tile(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, short_row, long_row);
+    rt::reduce_rows<KIND == 0>(a.tiles, a.n_rows, a.rowptr, kLongRow, lanes, st, lds, load_row, batch, finish);
 }
 
 template <typename T>
@@ -231,28 +221,26 @@ void launch(int pass, dim3 grid, hipStream_t s, const Args& a) {
 using namespace dgll;
 
 DGLL_API int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d) {
+    static const char* const kPass = "dgll_hip_sparse_attn_pass";
     DGLL_REQUIRE(d != nullptr, "the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_ATTN_FORWARD || d->pass == DGLL_ATTN_ROWS || d->pass == DGLL_ATTN_COLS,
                  "pass must be DGLL_ATTN_FORWARD, DGLL_ATTN_ROWS or DGLL_ATTN_COLS");
     if (const int rc = rt::require_head_pass(d->dtype, d->heads, d->D, d->n_rows, d->n_cols, d->rowptr, d->col)) return rc;
-    const int epv = d->dtype == DGLL_F32 ? 4 : 8;
-    DGLL_REQUIRE(d->q && d->k && d->v && d->out, "q, k, v and the pass's output matrix must be non-NULL");
-    const int64_t feat = (int64_t)d->heads * d->D;
-    DGLL_REQUIRE(rt::require_matrix(d->q, d->ld_q, epv, feat) && rt::require_matrix(d->k, d->ld_k, epv, feat) &&
-                     rt::require_matrix(d->v, d->ld_v, epv, feat) && rt::require_matrix(d->out, d->ld_out, epv, feat),
-                 "q, k, v and the output: 16-byte aligned base, a pitch of whole 16-byte vectors >= heads * D");
+    const auto [epv, esz] = rt::storage_of(d->dtype);
+    DGLL_REQUIRE_OPERAND(kPass, q, d->heads * d->D);
+    DGLL_REQUIRE_OPERAND(kPass, k, d->heads * d->D);
+    DGLL_REQUIRE_OPERAND(kPass, v, d->heads * d->D);
+    DGLL_REQUIRE_OPERAND(kPass, out, d->heads * d->D);
     DGLL_REQUIRE(!d->kv_shared || (d->k == d->v && d->ld_k == d->ld_v), "kv_shared: k and v must be the same buffer with the same pitch");
     if (d->pass == DGLL_ATTN_FORWARD) {
         DGLL_REQUIRE(d->lse != nullptr, "forward: lse must be non-NULL");
     } else {
-        DGLL_REQUIRE(rt::require_matrix(d->grad_out, d->ld_grad_out, epv, feat),
-                     "backward: grad_out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+        DGLL_REQUIRE_OPERAND(kPass, grad_out, d->heads * d->D);
         DGLL_REQUIRE(d->lse_delta != nullptr, "backward: lse_delta must be non-NULL");
         if (d->pass == DGLL_ATTN_ROWS) {
             DGLL_REQUIRE(d->lse != nullptr, "rows pass: lse must be non-NULL");
         } else {
-            DGLL_REQUIRE(rt::require_matrix(d->out2, d->ld_out2, epv, feat),
-                         "cols pass: out2 (dv) non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= heads * D");
+            DGLL_REQUIRE_OPERAND(kPass, out2, d->heads * d->D);          // dv
         }
     }
 
@@ -261,7 +249,6 @@ DGLL_API int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d) {
     a.col = d->col;
     a.n_rows = d->n_rows;
     a.n_cols = d->n_cols;
-    const int64_t esz = d->dtype == DGLL_F32 ? 4 : 2;
     a.q = static_cast<const char*>(d->q);         a.pb_q = d->ld_q * esz;
     a.k = static_cast<const char*>(d->k);         a.pb_k = d->ld_k * esz;
     a.v = static_cast<const char*>(d->v);         a.pb_v = d->ld_v * esz;
@@ -275,14 +262,10 @@ DGLL_API int dgll_hip_sparse_attn_pass(void* stream, const dgll_attn_desc* d) {
     a.scale = d->scale;
     a.kv_shared = d->kv_shared ? 1 : 0;
     const rt::HeadGeometry geo = rt::make_head_geometry(d->heads, d->D, epv, d->n_rows);
-    a.vph = geo.vph;
-    a.lph = geo.lph;
-    a.hpb = geo.hpb;
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
+    rt::set_geometry(a, geo);
     if (geo.grid == 0) return DGLL_OK;
-    DGLL_REQUIRE(geo.col_blocks <= 65535, "at most 65535 column blocks of whole heads");
-    const dim3 grid((unsigned)geo.grid, (unsigned)geo.col_blocks);
+    dim3 grid;
+    if (const int rc = rt::launch_grid(kPass, geo.grid, geo.col_blocks, 1, grid)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->dtype == DGLL_F32) sat::launch<float>(d->pass, grid, st, a);
     else sat::launch<bf16_t>(d->pass, grid, st, a);

@@ -288,11 +288,12 @@ bool launch(int pass, int bb, dim3 grid, hipStream_t s, const Args& a) {
 using namespace dgll;
 
 DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
+    static const char* const kPass = "dgll_hip_typed_spmm_pass";
     DGLL_REQUIRE(d != nullptr, "dgll_hip_typed_spmm_pass: the pass descriptor must be non-NULL");
     DGLL_REQUIRE(d->pass == DGLL_TYPED_EXPAND || d->pass == DGLL_TYPED_CONTRACT || d->pass == DGLL_TYPED_EDGE_DOTS,
                  "dgll_hip_typed_spmm_pass: pass must be DGLL_TYPED_EXPAND, DGLL_TYPED_CONTRACT or DGLL_TYPED_EDGE_DOTS");
     DGLL_REQUIRE(d->dtype == DGLL_F32 || d->dtype == DGLL_BF16, "dgll_hip_typed_spmm_pass: dtype must be DGLL_F32 or DGLL_BF16");
-    const int epv = d->dtype == DGLL_F32 ? 4 : 8;
+    const auto [epv, esz] = rt::storage_of(d->dtype);
     DGLL_REQUIRE(d->R >= 1 && d->B >= 1 && (int64_t)d->R * d->B < (1ll << 31),
                  "dgll_hip_typed_spmm_pass: R >= 1 edge types, B >= 1 bases, R * B < 2^31");
     DGLL_REQUIRE(d->F >= epv && d->F % epv == 0, "dgll_hip_typed_spmm_pass: F a positive multiple of the 16-byte vector width (4 fp32, 8 bf16 columns)");
@@ -305,17 +306,10 @@ DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
     const bool dots = d->pass == DGLL_TYPED_EDGE_DOTS, contract = d->pass == DGLL_TYPED_CONTRACT;
     if (!dots) {
         DGLL_REQUIRE(d->etype && d->coeff, "dgll_hip_typed_spmm_pass: expand / contract: etype and coeff must be non-NULL");
-        DGLL_REQUIRE(rt::require_matrix(d->out, d->ld_out, epv, contract ? d->F : wide),
-                     "dgll_hip_typed_spmm_pass: out non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= its width (expand B * F, contract F)");
+        DGLL_REQUIRE_OPERAND(kPass, out, contract ? d->F : d->B * d->F);
     }
-    if (!contract) {
-        DGLL_REQUIRE(rt::require_matrix(d->x, d->ld_x, epv, d->F),
-                     "dgll_hip_typed_spmm_pass: x non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= F");
-    }
-    if (d->pass != DGLL_TYPED_EXPAND) {
-        DGLL_REQUIRE(rt::require_matrix(d->dz, d->ld_dz, epv, wide),
-                     "dgll_hip_typed_spmm_pass: dz non-NULL, 16-byte aligned, a pitch of whole 16-byte vectors >= B * F");
-    }
+    if (!contract) DGLL_REQUIRE_OPERAND(kPass, x, d->F);
+    if (d->pass != DGLL_TYPED_EXPAND) DGLL_REQUIRE_OPERAND(kPass, dz, d->B * d->F);
     if (dots) {
         DGLL_REQUIRE(d->p && d->ld_p == ((int64_t)d->B + 3) / 4 * 4, "dgll_hip_typed_spmm_pass: p non-NULL with pitch ld_p = B rounded up to 4");
     }
@@ -328,7 +322,6 @@ DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
     a.coeff = d->coeff;
     a.n_rows = d->n_rows;
     a.n_cols = d->n_cols;
-    const int64_t esz = d->dtype == DGLL_F32 ? 4 : 2;
     a.x = static_cast<const char*>(contract ? d->dz : d->x);
     a.pb_x = (contract ? d->ld_dz : d->ld_x) * esz;
     a.h = static_cast<const char*>(d->dz);
@@ -341,19 +334,17 @@ DGLL_API int dgll_hip_typed_spmm_pass(void* stream, const dgll_typed_desc* d) {
     a.R = d->R;
     a.B = d->B;
     a.vpr = (int)vpr;
-    const rt::HeadGeometry geo = rt::make_row_geometry(rt::pow2_at_least(vpr < kWave ? vpr : kWave, rt::kMinGroup), d->n_rows);
-    a.lpr = geo.lpr;
-    a.tiles = geo.tiles;
-    a.chunks = (int)((vpr + a.lpr - 1) / a.lpr);
+    const rt::HeadGeometry geo = rt::make_flat_geometry(vpr, d->n_rows);
+    rt::set_geometry(a, geo);
+    a.chunks = geo.col_blocks;
     a.staged = (int64_t)d->R * d->B <= typed::kCoeffLds ? 1 : 0;
-    const int64_t gx = geo.grid;
-    if (gx == 0) return DGLL_OK;
-    // bases per block: the smallest compiled size that holds B, kBasisBlock for more
+    if (geo.grid == 0) return DGLL_OK;
+    // bases per block: the smallest compiled size that holds B, kBasisBlock for more (B <= 8 * 65535)
     int bb = 1;
     while (bb < typed::kBasisBlock && bb < d->B) bb <<= 1;
     const int64_t gz = contract ? 1 : ((int64_t)d->B + bb - 1) / bb;
-    DGLL_REQUIRE(gz <= 65535, "dgll_hip_typed_spmm_pass: at most 65535 basis blocks (B <= 8 * 65535)");
-    const dim3 grid((unsigned)gx, dots ? 1u : (unsigned)a.chunks, (unsigned)gz);
+    dim3 grid;
+    if (const int rc = rt::launch_grid(kPass, geo.grid, dots ? 1 : geo.col_blocks, gz, grid)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool found = d->dtype == DGLL_F32 ? typed::launch<float>(d->pass, bb, grid, st, a) : typed::launch<bf16_t>(d->pass, bb, grid, st, a);
     DGLL_REQUIRE(found, "dgll_hip_typed_spmm_pass: no kernel for this basis block size");

@@ -25,6 +25,11 @@ def _dtype_code(t):
         raise TypeError("dgll_amd kernels take float32 or bfloat16 matrices, got %s" % t.dtype)
 
 
+def epv(dtype):
+    """Elements of a 16-byte lane vector of `dtype` (float32 or bfloat16)."""
+    return 8 if dtype == torch.bfloat16 else 4
+
+
 def _row_major(x):
     """2-D tensor with unit column stride (any row stride >= ncols is passed through as the leading dimension)."""
     if x.dim() != 2:

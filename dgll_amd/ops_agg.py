@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, as_rows16
+from .ops import _dtype_code, epv, _require_cuda, as_rows16
 
 LONG_ROW = _lib.MAGG_LONG_ROW       # rows with more entries are swept by a whole workgroup
 AGGREGATORS = {"mean": _lib.MAGG_MEAN, "sum": _lib.MAGG_SUM, "max": _lib.MAGG_MAX, "min": _lib.MAGG_MIN, "var": _lib.MAGG_VAR,
@@ -42,10 +42,6 @@ SCALERS = {"identity": _lib.MAGG_IDENTITY, "amplification": _lib.MAGG_AMPLIFICAT
 _NOT_BUILT = ("moment3", "moment4", "moment5")
 _TAGS = ("magg_forward", "magg_rows", "magg_cols")
 _USE_STATS, _USE_ARG = (_lib.MAGG_VAR, _lib.MAGG_STD), (_lib.MAGG_MAX, _lib.MAGG_MIN)
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 def _desc(kind, graph, F, dtype, aggs, scalers, delta):
@@ -146,10 +142,10 @@ def _matrix(t, rows, name):
     _dtype_code(t)
     if t.dim() != 2 or t.shape[0] != rows:
         raise ValueError("multi_aggregate: %s must be a matrix of %d rows, got %s" % (name, rows, tuple(t.shape)))
-    F, epv = t.shape[1], _epv(t.dtype)
-    if F == 0 or F % epv:
+    F, vec = t.shape[1], epv(t.dtype)
+    if F == 0 or F % vec:
         raise ValueError("multi_aggregate: the width %d of %s is not a whole number of 16-byte vectors (%d columns of %s); the layers "
-                         "pad their widths with zero columns" % (F, name, epv, t.dtype))
+                         "pad their widths with zero columns" % (F, name, vec, t.dtype))
 
 
 def multi_aggregate(graph, x_src, y_dst=None, aggregators=("mean", "max", "min", "std"),

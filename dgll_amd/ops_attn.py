@@ -24,14 +24,10 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16
 
 LONG_ROW = _lib.ATTN_LONG_ROW       # rows with more entries are swept by a whole workgroup
 _MAX_VECTORS = 64                   # a head fits a wavefront's lanes: D / EPV <= 64
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 def _launch(kind, graph, heads, D, scale, shared, q, k, v, out, out2=None, grad_out=None, lse=None, lse_delta=None):
@@ -54,7 +50,7 @@ def _same_buffer(a, b):
 def sparse_attention_forward_raw(graph, q, k, v, heads, scale):
     """(out, lse) with no autograd; q / k / v as as_rows16 leaves them (k and v the same tensor: one gather per edge)."""
     D = q.shape[1] // heads
-    out = alloc_features(graph.n_rows, heads * D, q.dtype, q.device, pad_to=_epv(q.dtype))
+    out = alloc_features(graph.n_rows, heads * D, q.dtype, q.device, pad_to=epv(q.dtype))
     lse = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=q.device)
     _launch(_lib.ATTN_FORWARD, graph, heads, D, scale, _same_buffer(k, v), q, k, v, out, lse=lse)
     return out, lse
@@ -63,16 +59,16 @@ def sparse_attention_forward_raw(graph, q, k, v, heads, scale):
 def sparse_attention_backward_raw(graph, q, k, v, heads, scale, lse, g, need_kv=True):
     """(grad_q, grad_k or None, grad_v or None) from the output gradient g (rows on a 16-byte pitch)."""
     D = q.shape[1] // heads
-    epv = _epv(q.dtype)
+    vec = epv(q.dtype)
     shared = _same_buffer(k, v)
-    dq = alloc_features(graph.n_rows, heads * D, q.dtype, q.device, pad_to=epv)
+    dq = alloc_features(graph.n_rows, heads * D, q.dtype, q.device, pad_to=vec)
     lse_delta = torch.empty((graph.n_rows, 2 * heads), dtype=torch.float32, device=q.device)
     _launch(_lib.ATTN_ROWS, graph, heads, D, scale, shared, q, k, v, dq, grad_out=g, lse=lse, lse_delta=lse_delta)
     dk = dv = None
     if need_kv:
         gt, _ = graph.transpose()
-        dk = alloc_features(graph.n_cols, heads * D, q.dtype, q.device, pad_to=epv)
-        dv = alloc_features(graph.n_cols, heads * D, q.dtype, q.device, pad_to=epv)
+        dk = alloc_features(graph.n_cols, heads * D, q.dtype, q.device, pad_to=vec)
+        dv = alloc_features(graph.n_cols, heads * D, q.dtype, q.device, pad_to=vec)
         _launch(_lib.ATTN_COLS, gt, heads, D, scale, shared, q, k, v, dk, out2=dv, grad_out=g, lse_delta=lse_delta)
     return dq, dk, dv
 
@@ -116,12 +112,12 @@ def sparse_attention(graph, q, k, v, heads, scale=None):
     if heads < 1 or q.shape[1] % heads:
         raise ValueError("heads = %d does not divide the %d columns" % (heads, q.shape[1]))
     D = q.shape[1] // heads
-    epv = _epv(q.dtype)
-    if D == 0 or D % epv:
+    vec = epv(q.dtype)
+    if D == 0 or D % vec:
         raise ValueError("D = %d is not a whole number of 16-byte vectors (%d columns of %s); the layers pad their heads"
-                         % (D, epv, q.dtype))
-    if D // epv > _MAX_VECTORS:
-        raise ValueError("D = %d: a head may span at most %d columns of %s (64 16-byte vectors)" % (D, _MAX_VECTORS * epv, q.dtype))
+                         % (D, vec, q.dtype))
+    if D // vec > _MAX_VECTORS:
+        raise ValueError("D = %d: a head may span at most %d columns of %s (64 16-byte vectors)" % (D, _MAX_VECTORS * vec, q.dtype))
     scale = float(D) ** -0.5 if scale is None else float(scale)
     if graph.n_rows == 0 or graph.nnz == 0:         # nothing to gather: zeros, with zero gradients
         return q.new_zeros((graph.n_rows, heads * D)) + 0 * (q.sum() + k.sum() + v.sum())

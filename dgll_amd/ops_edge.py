@@ -7,11 +7,7 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
-
-
-def _epv(dtype):
-    return 8 if dtype == torch.bfloat16 else 4
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16
 
 
 def _ready(x):
@@ -20,7 +16,7 @@ def _ready(x):
 
 
 def _empty_padded(n, width, dtype, device):
-    return alloc_features(n, width, dtype, device, pad_to=_epv(dtype))
+    return alloc_features(n, width, dtype, device, pad_to=epv(dtype))
 
 
 def _ws(plan, heads, fo, dev, other_plan=None):
@@ -38,7 +34,7 @@ def sddmm_raw(graph, g, b):
     if g.dtype != b.dtype:
         b = b.to(g.dtype)
     feat = g.shape[1]
-    tile = 64 * _epv(g.dtype)
+    tile = 64 * epv(g.dtype)
     out = torch.empty(graph.nnz, dtype=torch.float32, device=g.device)
     total = None
     for c0 in range(0, feat, tile):  # > 64 vectors per row: column blocks, summed
@@ -97,14 +93,14 @@ def head_width_padded(fo, dtype, pow2=True):
     """Per-head column count the kernels need: a whole number of 16-byte vectors -- a power of two of them for the
     first-generation kernels (max-subtracted softmax, attention dropout given as an edge_scale array), any number for
     sparseGatConv's form, with or without dropout drawn in the kernels."""
-    epv = _epv(dtype)
-    vecs = -(-fo // epv)
+    vec = epv(dtype)
+    vecs = -(-fo // vec)
     if not pow2:
-        return vecs * epv
+        return vecs * vec
     p = 1
     while p < vecs:
         p <<= 1
-    return p * epv
+    return p * vec
 
 
 def _row_slot(x, byte_off, n_floats):

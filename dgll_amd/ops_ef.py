@@ -27,15 +27,11 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16
 
 LONG_ROW = _lib.EF_LONG_ROW         # rows with more entries are swept by a whole workgroup
 _TAGS = ("ef_forward", "ef_cols", "ef_edge")
 _OPS = {("add", None): _lib.EF_ADD, ("add", "relu"): _lib.EF_ADD_RELU, ("mul", None): _lib.EF_MUL}
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 def _launch(kind, op, gr, perm, nnz, scale, ref, x=None, e=None, g=None, out=None, gx=None, ge=None):
@@ -62,7 +58,7 @@ def mean_scale(graph):
 # x, e, g: matrices with rows on a 16-byte pitch; op: an _lib.EF_* code; scale: fp32 [n_dst] or None.  Operands the (pass, op) does
 # not read are not passed on, whatever the caller gave.
 def forward_raw(graph, x, e, op, scale=None):
-    out = alloc_features(graph.n_rows, x.shape[1], x.dtype, x.device, pad_to=_epv(x.dtype))
+    out = alloc_features(graph.n_rows, x.shape[1], x.dtype, x.device, pad_to=epv(x.dtype))
     _launch(_lib.EF_FORWARD, op, graph, None, graph.nnz, scale, x, x=x, e=e, out=out)
     return out
 
@@ -70,7 +66,7 @@ def forward_raw(graph, x, e, op, scale=None):
 def cols_raw(graph, x, e, g, op, scale=None):
     """grad_x [n_src, F] over graph.transpose()."""
     gt, perm = graph.transpose()
-    gx = alloc_features(gt.n_rows, g.shape[1], g.dtype, g.device, pad_to=_epv(g.dtype))
+    gx = alloc_features(gt.n_rows, g.shape[1], g.dtype, g.device, pad_to=epv(g.dtype))
     read_e = op != _lib.EF_ADD
     _launch(_lib.EF_COLS, op, gt, perm if read_e else None, graph.nnz, scale, g, x=x if op == _lib.EF_ADD_RELU else None,
             e=e if read_e else None, g=g, gx=gx)
@@ -79,7 +75,7 @@ def cols_raw(graph, x, e, g, op, scale=None):
 
 def edge_raw(graph, x, e, g, op, scale=None, out=None):
     """grad_e [nnz, F] in the graph's entry order (out: a [nnz, F] buffer of any 16-byte pitch to write instead of a new one)."""
-    ge = alloc_features(graph.nnz, g.shape[1], g.dtype, g.device, pad_to=_epv(g.dtype)) if out is None else out
+    ge = alloc_features(graph.nnz, g.shape[1], g.dtype, g.device, pad_to=epv(g.dtype)) if out is None else out
     _launch(_lib.EF_EDGE, op, graph, None, graph.nnz, scale, g, x=x if op != _lib.EF_ADD else None,
             e=e if op == _lib.EF_ADD_RELU else None, g=g, ge=ge)
     return ge
@@ -134,10 +130,10 @@ def u_op_e_sum(graph, x, e, op="add", act=None, reduce="sum"):
     if e.shape[1] != x.shape[1]:
         raise ValueError("u_op_e_sum: e has %d columns and x %d: edge features of another width than the node features' are not "
                          "built (project them first, as nn.GINE does)" % (e.shape[1], x.shape[1]))
-    F, epv = x.shape[1], _epv(x.dtype)
-    if F == 0 or F % epv:
+    F, vec = x.shape[1], epv(x.dtype)
+    if F == 0 or F % vec:
         raise ValueError("u_op_e_sum: the width %d is not a whole number of 16-byte vectors (%d columns of %s); the layers pad "
-                         "their widths with zero columns" % (F, epv, x.dtype))
+                         "their widths with zero columns" % (F, vec, x.dtype))
     _require_cuda(x, e, graph.rowptr)
     if graph.n_rows == 0 or graph.nnz == 0:     # nothing to gather: zeros, with zero gradients
         return x.new_zeros((graph.n_rows, F)) + 0 * (x.sum() + e.sum())

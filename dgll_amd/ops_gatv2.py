@@ -23,14 +23,10 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16
 
 LONG_ROW = _lib.GATV2_LONG_ROW      # rows with more entries are swept by a whole workgroup
 _MAX_PARTIALS = 2048                # workgroups of the rows pass = rows of the grad_attn partials
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 def _launch(kind, graph, heads, D, slope, xl, xr, attn, out, grad_out=None, lse=None, lse_delta=None, part=None, dattn=None):
@@ -50,7 +46,7 @@ def _launch(kind, graph, heads, D, slope, xl, xr, attn, out, grad_out=None, lse=
 def gatv2_forward_raw(graph, xl, xr, attn, heads, slope):
     """(out, lse) with no autograd; xl / xr as as_rows16 leaves them, attn fp32 [heads, D] contiguous."""
     D = attn.shape[1]
-    out = alloc_features(graph.n_rows, heads * D, xl.dtype, xl.device, pad_to=_epv(xl.dtype))
+    out = alloc_features(graph.n_rows, heads * D, xl.dtype, xl.device, pad_to=epv(xl.dtype))
     lse = torch.empty((graph.n_rows, heads), dtype=torch.float32, device=xl.device)
     _launch(_lib.GATV2_FORWARD, graph, heads, D, slope, xl, xr, attn, out, lse=lse)
     return out, lse
@@ -59,8 +55,8 @@ def gatv2_forward_raw(graph, xl, xr, attn, heads, slope):
 def gatv2_backward_raw(graph, xl, xr, attn, heads, slope, lse, g, need_xl=True):
     """(grad_xl or None, grad_xr, grad_attn fp32 [heads, D]) from the output gradient g (rows on a 16-byte pitch)."""
     D = attn.shape[1]
-    epv = _epv(xl.dtype)
-    dxr = alloc_features(graph.n_rows, heads * D, xl.dtype, xl.device, pad_to=epv)
+    vec = epv(xl.dtype)
+    dxr = alloc_features(graph.n_rows, heads * D, xl.dtype, xl.device, pad_to=vec)
     lse_delta = torch.empty((graph.n_rows, 2 * heads), dtype=torch.float32, device=xl.device)
     part = torch.empty((max(1, min(_MAX_PARTIALS, -(-graph.n_rows // 16))), heads * D), dtype=torch.float32, device=xl.device)
     dattn = torch.empty((heads, D), dtype=torch.float32, device=xl.device)      # the partials summed in workgroup order, by the same call
@@ -68,7 +64,7 @@ def gatv2_backward_raw(graph, xl, xr, attn, heads, slope, lse, g, need_xl=True):
     dxl = None
     if need_xl:
         gt, _ = graph.transpose()
-        dxl = alloc_features(graph.n_cols, heads * D, xl.dtype, xl.device, pad_to=epv)
+        dxl = alloc_features(graph.n_cols, heads * D, xl.dtype, xl.device, pad_to=vec)
         _launch(_lib.GATV2_TRANSPOSED, gt, heads, D, slope, xl, xr, attn, dxl, grad_out=g, lse_delta=lse_delta)
     return dxl, dxr, dattn
 
@@ -112,9 +108,9 @@ def gatv2_aggregate(graph, xl, xr, attn, heads, negative_slope=0.2):
     if attn.dim() != 2 or heads < 1 or attn.shape[0] != heads or heads * attn.shape[1] != xl.shape[1]:
         raise ValueError("attn must be [heads, D] with heads * D = %d columns" % xl.shape[1])
     D = int(attn.shape[1])
-    if D == 0 or D % _epv(xl.dtype):
+    if D == 0 or D % epv(xl.dtype):
         raise ValueError("D = %d is not a whole number of 16-byte vectors (%d columns of %s); nn.GATv2Conv pads its heads"
-                         % (D, _epv(xl.dtype), xl.dtype))
+                         % (D, epv(xl.dtype), xl.dtype))
     if graph.n_rows == 0 or graph.nnz == 0:         # nothing to gather: zeros, with zero gradients
         return xl.new_zeros((graph.n_rows, heads * D)) + 0 * (xl.sum() + xr.sum() + attn.sum().to(xl.dtype))
     return _Gatv2.apply(xl, xr, attn, graph, heads, float(negative_slope))

@@ -36,15 +36,11 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16
 
 LONG_ROW = _lib.MP_LONG_ROW         # rows with more entries are swept by a whole workgroup
 _MAX_VECTORS = 64                   # a head fits a wavefront's lanes: D / EPV <= 64
 _TAGS = ("mp_edge_softmax", "mp_edge_softmax_bwd", "mp_e_sum", "mp_u_add_v", "mp_u_mul_e_sum", "mp_u_dot_v")
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 def _ld(t):
@@ -110,7 +106,7 @@ def u_add_v_raw(graph, a, b, heads, transposed=False):
 def u_mul_e_sum_raw(graph, x, w, heads, transposed=False):
     """x (rows on a 16-byte pitch) gathered by the pass's CSR, weighted by w [nnz, heads] at the entries' slots."""
     gr, perm = _over(graph, transposed)
-    out = alloc_features(gr.n_rows, x.shape[1], x.dtype, x.device, pad_to=_epv(x.dtype))
+    out = alloc_features(gr.n_rows, x.shape[1], x.dtype, x.device, pad_to=epv(x.dtype))
     _launch(_lib.MP_U_MUL_E_SUM, gr, perm, heads, x.shape[1] // heads, _dtype_code(x), e=w, x=x, out=out)
     return out
 
@@ -241,12 +237,12 @@ def _node_matrix(t, rows, heads, name, what):
         raise ValueError("%s: %s must be a matrix of %d rows, got %s" % (name, what, rows, tuple(t.shape)))
     if heads < 1 or t.shape[1] % heads:
         raise ValueError("%s: heads = %d does not divide the %d columns of %s" % (name, heads, t.shape[1], what))
-    D, epv = t.shape[1] // heads, _epv(t.dtype)
-    if D == 0 or D % epv:
+    D, vec = t.shape[1] // heads, epv(t.dtype)
+    if D == 0 or D % vec:
         raise ValueError("%s: D = %d is not a whole number of 16-byte vectors (%d columns of %s); the layers pad their heads"
-                         % (name, D, epv, t.dtype))
-    if D // epv > _MAX_VECTORS:
-        raise ValueError("%s: D = %d: a head may span at most %d columns of %s (64 16-byte vectors)" % (name, D, _MAX_VECTORS * epv, t.dtype))
+                         % (name, D, vec, t.dtype))
+    if D // vec > _MAX_VECTORS:
+        raise ValueError("%s: D = %d: a head may span at most %d columns of %s (64 16-byte vectors)" % (name, D, _MAX_VECTORS * vec, t.dtype))
     return D
 
 

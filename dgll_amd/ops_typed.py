@@ -24,15 +24,11 @@ import torch
 
 from . import _lib
 from .graph import CSRGraph
-from .ops import _dtype_code, _require_cuda, alloc_features, as_rows16, spmm_raw
+from .ops import _dtype_code, epv, _require_cuda, alloc_features, as_rows16, spmm_raw
 
 LONG_ROW = _lib.TYPED_LONG_ROW          # rows with more entries are swept by a whole workgroup
 COEFF_LDS = _lib.TYPED_COEFF_LDS        # the kernels stage coeff in LDS up to this many entries (num_rels * B), else read it from global memory
 BASIS_BLOCK = _lib.TYPED_BASIS_BLOCK    # bases one launch block accumulates; more bases re-gather x once per block
-
-
-def _epv(dtype):
-    return 4 if dtype == torch.float32 else 8
 
 
 class TypedEdges:
@@ -135,7 +131,7 @@ def typed_spmm_forward_raw(graph, edges, x, coeff, out=None):
     """Z [n_dst, B * F] with no autograd; x as as_rows16 leaves it, coeff fp32 [num_rels, B] contiguous.  out: rows of a caller's
     buffer to write (16-byte pitch)."""
     B, F = coeff.shape[1], x.shape[1]
-    z = alloc_features(graph.n_rows, B * F, x.dtype, x.device, pad_to=_epv(x.dtype)) if out is None else out
+    z = alloc_features(graph.n_rows, B * F, x.dtype, x.device, pad_to=epv(x.dtype)) if out is None else out
     _launch(_lib.TYPED_EXPAND, graph, edges.etypes, edges.norm, edges.num_rels, B, F, coeff, x=x, out=z)
     return z
 
@@ -147,7 +143,7 @@ def typed_spmm_backward_raw(graph, edges, x, coeff, g, need_x=True, need_coeff=T
     if need_x:
         gt, _ = graph.transpose()
         t_etypes, t_norm = edges.transposed()
-        dx = alloc_features(graph.n_cols, F, x.dtype, x.device, pad_to=_epv(x.dtype))
+        dx = alloc_features(graph.n_cols, F, x.dtype, x.device, pad_to=epv(x.dtype))
         _launch(_lib.TYPED_CONTRACT, gt, t_etypes, t_norm, edges.num_rels, B, F, coeff, dz=g, out=dx)
     if need_coeff:
         p = torch.empty((graph.nnz, (B + 3) // 4 * 4), dtype=torch.float32, device=x.device)
@@ -195,9 +191,9 @@ def typed_spmm(graph, edges, x, coeff):
         raise ValueError("x has %d rows but the graph gathers from %d sources" % (x.shape[0], graph.n_cols))
     if coeff.shape[0] != edges.num_rels or coeff.shape[1] < 1:
         raise ValueError("coeff must be [num_rels = %d, B >= 1], got %s" % (edges.num_rels, tuple(coeff.shape)))
-    F, B, epv = x.shape[1], coeff.shape[1], _epv(x.dtype)
-    if F == 0 or F % epv:
-        raise ValueError("F = %d is not a whole number of 16-byte vectors (%d columns of %s); the layer pads its input" % (F, epv, x.dtype))
+    F, B, vec = x.shape[1], coeff.shape[1], epv(x.dtype)
+    if F == 0 or F % vec:
+        raise ValueError("F = %d is not a whole number of 16-byte vectors (%d columns of %s); the layer pads its input" % (F, vec, x.dtype))
     if graph.n_rows == 0 or graph.nnz == 0:         # nothing to gather: zeros, with zero gradients
         return x.new_zeros((graph.n_rows, B * F)) + 0 * (x.sum() + coeff.sum().to(x.dtype))
     return _TypedSpmm.apply(x, coeff, graph, edges)

@@ -95,6 +95,24 @@ def test_table_is_what_row_tiles_hpp_gives(tmp_path_factory):
             assert line == tuple(c.geo) + (tiles, tiles), (R.case_id(c), n, line)
 
 
+def test_flat_geometry_is_the_formula(tmp_path_factory):
+    """make_flat_geometry (the passes whose rows are F columns without heads: typed SpMM, PNA, edge features) against its formula
+    restated: vpr below, at and above the lane-width steps and the 64-lane cap, with no rows, one row and a ragged last tile."""
+    exe = build_emulator(tmp_path_factory, "row_tiles.hpp", "geometry_main.cpp")
+    cases = [(vpr, n_rows) for vpr in (1, 6, 8, 9, 33, 64, 65, 130) for n_rows in (0, 1, 33)]
+    res = subprocess.run([exe, "flat"] + [str(v) for c in cases for v in c], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stderr
+    lines = [tuple(int(v) for v in ln.split()) for ln in res.stdout.splitlines()]
+    assert len(lines) == len(cases)
+    for (vpr, n_rows), line in zip(cases, lines):
+        lpr = 8
+        while lpr < min(vpr, 64):
+            lpr *= 2
+        groups = 4 * 64 // lpr
+        tiles = -(-n_rows // groups)
+        assert line == (lpr, -(-vpr // lpr), tiles, min(tiles, 2 ** 22)), (vpr, n_rows, line)
+
+
 def test_table_reaches_every_pair_and_condition():
     for dt in (F32, BF16):
         cases = [c for c in CASES if c.dtype == dt]
