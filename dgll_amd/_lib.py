@@ -169,6 +169,25 @@ EF_ADD, EF_ADD_RELU, EF_MUL = 0, 1, 2
 EF_LONG_ROW = 256           # DGLL_EF_LONG_ROW of include/dgll_hip.h
 
 
+class GatedDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_gated_desc (dgll_hip_gated_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("F", C.c_int64), ("eps", C.c_float),
+                ("a", C.c_void_p), ("ld_a", C.c_int64), ("b", C.c_void_p), ("ld_b", C.c_int64),
+                ("c", C.c_void_p), ("ld_c", C.c_int64), ("v", C.c_void_p), ("ld_v", C.c_int64),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("ehat", C.c_void_p), ("ld_ehat", C.c_int64),
+                ("inv_s", C.c_void_p), ("ld_inv_s", C.c_int64), ("out32", C.c_void_p), ("ld_out32", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("grad_ehat", C.c_void_p), ("ld_grad_ehat", C.c_int64),
+                ("grad_c", C.c_void_p), ("ld_grad_c", C.c_int64), ("grad_a", C.c_void_p), ("ld_grad_a", C.c_int64),
+                ("w", C.c_void_p), ("ld_w", C.c_int64), ("grad_b", C.c_void_p), ("ld_grad_b", C.c_int64),
+                ("grad_v", C.c_void_p), ("ld_grad_v", C.c_int64)]
+
+
+GATED_FORWARD, GATED_ROWS, GATED_COLS = 0, 1, 2
+GATED_LONG_ROW = 256        # DGLL_GATED_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -317,6 +336,7 @@ SIGNATURES = {
     "dgll_hip_mp_pass": (_i32, [_vp, C.POINTER(MpDesc)]),
     "dgll_hip_multi_agg_pass": (_i32, [_vp, C.POINTER(MultiAggDesc)]),
     "dgll_hip_edge_feat_pass": (_i32, [_vp, C.POINTER(EdgeFeatDesc)]),
+    "dgll_hip_gated_pass": (_i32, [_vp, C.POINTER(GatedDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

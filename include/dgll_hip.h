@@ -1120,6 +1120,57 @@ typedef struct dgll_edge_feat_desc {
 } dgll_edge_feat_desc;
 int dgll_hip_edge_feat_pass(void* stream, const dgll_edge_feat_desc* d);
 
+/* ---- Edge-gated aggregation with edge outputs (Bresson & Laurent's residual gated graph convnet, DGL's GatedGCNConv) and its exact
+ * backward; three passes behind one entry point (csrc/gated.hip).  Entry k of row i of A (rowptr / col, [n_dst x n_src], rectangular
+ * allowed, edge values are not read) is the edge j = col[k] -> i; per-edge matrices are in A's entry order; duplicate entries are
+ * separate edges.  For every column independently, with a [n_dst, F], b and v [n_src, F], c [nnz, F]:
+ *     ehat[k] = c[k] + a[i] + b[j]     sig[k] = sigmoid(ehat[k])     S_i = sum_k sig[k] + eps     out[i] = (sum_k sig[k] v[j]) / S_i
+ * ehat is rounded to `dtype` when stored and every pass, the forward included, takes the sigmoid of that stored value (fp32, exp2 form;
+ * a saturated gate is exactly 0 or 1), so the gate itself is never stored.  With g = grad_out and ge = grad_ehat (NULL: zeros):
+ *     t[k] = ge[k] + g[i] (v[j] - out[i]) / S_i sig[k] (1 - sig[k])      grad_c[k] = t[k]      grad_a[i] = sum over row i of t[k]
+ *     grad_b[j] = sum over column j of t[k]                               grad_v[j] = sum over column j of sig[k] g[i] / S_i
+ *   DGLL_GATED_FORWARD  rowptr / col = A (n_rows = n_dst, n_cols = n_src).  Reads a (held), b and v (gathered), c (streamed at slot k);
+ *                       writes ehat [nnz, F], out [n_rows, F] (a row without entries: zeros) and the fp32 row state inv_s = 1 / S_i and
+ *                       out32 = the unrounded out_i, both [n_rows, F].
+ *   DGLL_GATED_ROWS     rowptr / col = A.  Reads grad_out, inv_s, out32 (held), v (gathered), ehat and grad_ehat (optional) at slot k;
+ *                       writes grad_c [nnz, F] (t, rounded to `dtype`), grad_a [n_rows, F] (the fp32 sum of the unrounded t) and, when
+ *                       w is non-NULL, w [n_rows, F] = grad_out / S_i for the cols pass.  grad_c and grad_a go together; with both NULL
+ *                       the pass reads no per-edge operand and only leaves w.
+ *   DGLL_GATED_COLS     rowptr / col = A^T (n_rows = n_src, n_cols = n_dst) with perm, A^T's entry k' -> A's entry (graph.transpose()).
+ *                       grad_b [n_rows, F] (when non-NULL) sums grad_c at slot perm[k'], the stored and so rounded t; grad_v [n_rows, F]
+ *                       (when non-NULL) sums sigmoid(ehat at slot perm[k']) * w[col[k']].  At least one of the two; zeros for a source
+ *                       no row references.
+ * Operands a pass does not read may be NULL and are not dereferenced.  nnz: the rows of the per-edge matrices (perm values are clamped
+ * to [0, nnz), col values used for addressing to [0, n_cols)).  Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation) but
+ * for the fp32 row state; pitches ld_* in elements, each its own: whole 16-byte vectors of `dtype` >= F, 16-byte aligned bases.  F a
+ * positive multiple of the vector width (4 fp32 / 8 bf16 columns); widths past 64 vectors go to column blocks.  Rows longer than
+ * DGLL_GATED_LONG_ROW entries are swept by a whole workgroup and merged through LDS in group order.  No atomics: two runs give the
+ * same bits.  No pass allocates, synchronises or reads anything back: the calls can be captured into a graph.  n_rows == 0 launches
+ * nothing.                                                                                                                           */
+enum { DGLL_GATED_FORWARD = 0, DGLL_GATED_ROWS = 1, DGLL_GATED_COLS = 2 };
+#define DGLL_GATED_LONG_ROW 256
+typedef struct dgll_gated_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int64_t F; float eps;
+    const void* a; int64_t ld_a;
+    const void* b; int64_t ld_b;
+    const void* c; int64_t ld_c;
+    const void* v; int64_t ld_v;
+    void* out; int64_t ld_out;
+    void* ehat; int64_t ld_ehat;
+    float* inv_s; int64_t ld_inv_s;
+    float* out32; int64_t ld_out32;
+    const void* grad_out; int64_t ld_grad_out;
+    const void* grad_ehat; int64_t ld_grad_ehat;
+    void* grad_c; int64_t ld_grad_c;
+    void* grad_a; int64_t ld_grad_a;
+    void* w; int64_t ld_w;
+    void* grad_b; int64_t ld_grad_b;
+    void* grad_v; int64_t ld_grad_v;
+} dgll_gated_desc;
+int dgll_hip_gated_pass(void* stream, const dgll_gated_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
