@@ -188,6 +188,21 @@ GATED_FORWARD, GATED_ROWS, GATED_COLS = 0, 1, 2
 GATED_LONG_ROW = 256        # DGLL_GATED_LONG_ROW of include/dgll_hip.h
 
 
+class ResGatedDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_res_gated_desc (dgll_hip_res_gated_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("F", C.c_int64), ("mean", C.c_int),
+                ("k", C.c_void_p), ("ld_k", C.c_int64), ("q", C.c_void_p), ("ld_q", C.c_int64),
+                ("v", C.c_void_p), ("ld_v", C.c_int64), ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("grad_k", C.c_void_p), ("ld_grad_k", C.c_int64),
+                ("grad_q", C.c_void_p), ("ld_grad_q", C.c_int64), ("grad_v", C.c_void_p), ("ld_grad_v", C.c_int64)]
+
+
+RES_GATED_FORWARD, RES_GATED_ROWS, RES_GATED_COLS = 0, 1, 2
+RES_GATED_LONG_ROW = 256    # DGLL_RES_GATED_LONG_ROW of include/dgll_hip.h
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -337,6 +352,7 @@ SIGNATURES = {
     "dgll_hip_multi_agg_pass": (_i32, [_vp, C.POINTER(MultiAggDesc)]),
     "dgll_hip_edge_feat_pass": (_i32, [_vp, C.POINTER(EdgeFeatDesc)]),
     "dgll_hip_gated_pass": (_i32, [_vp, C.POINTER(GatedDesc)]),
+    "dgll_hip_res_gated_pass": (_i32, [_vp, C.POINTER(ResGatedDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -20,8 +20,8 @@ just leaves w.  A gradient nobody asked for is neither computed nor returned.  N
 nothing allocated by a pass, synchronised or read back (the step can be captured), fp32 accumulation.  There is no CPU
 implementation here: a CPU tensor raises (the layer has a host path of its own).
 
-Not built: the variant without edge features (PyG's ResGatedGraphConv: the gate from a and b alone), ehat written in place over c,
-a fused projection of c, the partitioned (multi-GPU) path.
+Not built: ehat written in place over c, a fused projection of c, the partitioned (multi-GPU) path.  The variant without edge
+features (PyG's ResGatedGraphConv: the gate from two node rows alone, nothing stored per edge) is ops_res_gated.
 """
 import ctypes as C
 

@@ -1171,6 +1171,46 @@ typedef struct dgll_gated_desc {
 } dgll_gated_desc;
 int dgll_hip_gated_pass(void* stream, const dgll_gated_desc* d);
 
+/* ---- Gated aggregation with nothing stored per edge (the residual gated graph convnet without edge features: PyG's
+ * ResGatedGraphConv) and its exact backward; three passes behind one entry point (csrc/res_gated.hip).  Entry e of row i of A
+ * (rowptr / col, [n_dst x n_src], rectangular allowed, edge values are not read) is the edge j = col[e] -> i; duplicate entries are
+ * separate edges.  For every column independently, with k [n_dst, F], q and v [n_src, F] and g = grad_out [n_dst, F]:
+ *     s = sigmoid(k[i] + q[j])        out[i] = sum_e s v[j]        (mean != 0: divided by the row's entry count)
+ *     grad_k[i] = g[i] sum_e s (1 - s) v[j]      grad_q[j] = v[j] sum over column j of g[i] s (1 - s)      grad_v[j] = sum over column j of g[i] s
+ * The gate is the same fp32 function of the same stored k and q in every pass (1 / (1 + exp2(-x log2 e)): a saturated gate is exactly
+ * 0 or 1, and s (1 - s) then exactly 0) and is never stored: no pass reads or writes an [nnz, F] array.
+ *   DGLL_RES_GATED_FORWARD  rowptr / col = A (n_rows = n_dst, n_cols = n_src).  Reads k (held), q and v (gathered); writes out
+ *                           [n_rows, F] (a row without entries: zeros), scaled by 1 / (its entry count) in fp32 before the one store
+ *                           when mean != 0.
+ *   DGLL_RES_GATED_ROWS     rowptr / col = A.  Reads k and grad_out (held), q and v (gathered); writes grad_k [n_rows, F].
+ *   DGLL_RES_GATED_COLS     rowptr / col = A^T (n_rows = n_src, n_cols = n_dst; graph.transpose()'s structure, its permutation is not
+ *                           used).  Reads q (held), k and grad_out (gathered at col[e']) and, for grad_q, v (the row's own, at its end);
+ *                           writes grad_q and grad_v [n_rows, F], either of which may be NULL (not both): what only the missing one
+ *                           needs is neither loaded nor summed.  Zeros for a source no row references.
+ * `mean` is read by FORWARD alone (the backward of a mean takes grad_out already divided by the entry counts).  col values used for
+ * addressing are clamped to [0, n_cols).  Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation); pitches ld_* in elements,
+ * each its own: whole 16-byte vectors of `dtype` >= F, 16-byte aligned bases; the columns behind F are never read into a result and
+ * never written.  F a positive multiple of the vector width (4 fp32 / 8 bf16 columns); widths past 64 vectors go to column blocks.
+ * Rows longer than DGLL_RES_GATED_LONG_ROW entries are swept by a whole workgroup and merged through LDS in group order.  No atomics:
+ * two runs give the same bits.  No pass allocates, synchronises or reads anything back: the calls can be captured into a graph.
+ * n_rows == 0 launches nothing.                                                                                                      */
+enum { DGLL_RES_GATED_FORWARD = 0, DGLL_RES_GATED_ROWS = 1, DGLL_RES_GATED_COLS = 2 };
+#define DGLL_RES_GATED_LONG_ROW 256
+typedef struct dgll_res_gated_desc {
+    int pass; int dtype;
+    const int64_t* rowptr; const int32_t* col; int64_t n_rows; int64_t n_cols;
+    int64_t F; int mean;
+    const void* k; int64_t ld_k;
+    const void* q; int64_t ld_q;
+    const void* v; int64_t ld_v;
+    const void* grad_out; int64_t ld_grad_out;
+    void* out; int64_t ld_out;
+    void* grad_k; int64_t ld_grad_k;
+    void* grad_q; int64_t ld_grad_q;
+    void* grad_v; int64_t ld_grad_v;
+} dgll_res_gated_desc;
+int dgll_hip_res_gated_pass(void* stream, const dgll_res_gated_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
