@@ -203,6 +203,24 @@ RES_GATED_FORWARD, RES_GATED_ROWS, RES_GATED_COLS = 0, 1, 2
 RES_GATED_LONG_ROW = 256    # DGLL_RES_GATED_LONG_ROW of include/dgll_hip.h
 
 
+class EdgeProjDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_edge_proj_desc (dgll_hip_edge_proj_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int), ("op", C.c_int), ("De", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("F", C.c_int64), ("scale", C.c_void_p),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("a", C.c_void_p), ("ld_a", C.c_int64),
+                ("weight", C.c_void_p), ("bias", C.c_void_p),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("grad_x", C.c_void_p), ("ld_grad_x", C.c_int64), ("grad_a", C.c_void_p), ("ld_grad_a", C.c_int64),
+                ("dots_part", C.c_void_p), ("slabs", C.c_void_p), ("partials", C.c_int64)]
+
+
+EFP_FORWARD, EFP_COLS, EFP_PARAM, EFP_DOTS = 0, 1, 2, 3
+EFP_LONG_ROW = 256          # DGLL_EFP_LONG_ROW of include/dgll_hip.h
+EFP_MAX_DE = 16             # DGLL_EFP_MAX_DE: the widest edge attribute row
+EFP_MAX_PARTIALS = 512      # DGLL_EFP_MAX_PARTIALS: workgroups (and slabs) of the PARAM pass at the most
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -353,6 +371,7 @@ SIGNATURES = {
     "dgll_hip_edge_feat_pass": (_i32, [_vp, C.POINTER(EdgeFeatDesc)]),
     "dgll_hip_gated_pass": (_i32, [_vp, C.POINTER(GatedDesc)]),
     "dgll_hip_res_gated_pass": (_i32, [_vp, C.POINTER(ResGatedDesc)]),
+    "dgll_hip_edge_proj_pass": (_i32, [_vp, C.POINTER(EdgeProjDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,8 +1,9 @@
 """Graph isomorphism layer with edge features (DGL's GINEConv, "Strategies for Pre-training Graph Neural Networks": argument names,
 parameter name and shape) on the gfx950 aggregation engine.
 
-    GINEConv(apply_func=None, init_eps=0, learn_eps=False)
-    GINE(nfeat, edge_feat, nhid, nclass, n_layers=2)      a model of GINEConv layers, each with its own encoder of the edge attributes
+    GINEConv(apply_func=None, init_eps=0, learn_eps=False, edge_dim=None, in_feats=None)
+    GINE(nfeat, edge_feat, nhid, nclass, n_layers=2, fused_edge=False)
+                                                          a model of GINEConv layers, each with its own encoder of the edge attributes
 
 Over the entries j of row i of the graph (a CSRGraph [n_dst x n_src], anything as_csr_graph takes; rectangular blocks of
 NeighborSampler allowed; edge values are ignored), with e_ij the feature row of that entry, of the node features' width and in the
@@ -16,9 +17,14 @@ h_j + e_ij nor its relu exists per edge, and the backward recomputes the gate.  
 16-byte vectors is padded with zero columns on h and e alike (relu(0 + 0) = 0) and unpadded after the aggregation.  Edge attributes
 of another width go through a Linear first, which is what GINE does per layer.  Host tensors take `_host_aggregate`, the same
 semantics with torch's index ops, so that the layer's own logic can be exercised without a GPU; a GPU tensor never reaches it.
+
+With edge_dim (PyG's argument; in_feats, the node width, is then required) the layer owns that Linear as `lin` (PyG's name) and
+forward takes the RAW attributes [nnz, edge_dim], edge_dim <= 16: e_ij = lin(a_ij) is formed inside the aggregation kernel
+(ops_efp.u_op_proj_e_sum) and no [nnz, F] array exists in the forward or the backward.  GINE(fused_edge=True) hands each layer its
+encoder's weight and bias that way; parameters and state_dict() keys are the same either way.
 """
 from ... import backend as F
-from ... import ops_edge, ops_ef
+from ... import ops_edge, ops_ef, ops_efp
 from ...graph import as_csr_graph
 from .agnnconv import _linear
 from .dotgatconv import _split_feat
@@ -53,13 +59,41 @@ def _aggregate(graph, h_src, e, op, act=None):
     return out[:, :width] if pad else out
 
 
+def _aggregate_projected(graph, h_src, a, lin):
+    """sum over the entries of relu(h_src[col_k] + lin(a[k])), lin a Linear(edge_dim, F): ops_efp.u_op_proj_e_sum on the GPU (h and
+    the weight's output columns zero-padded to a whole 16-byte vector: relu(0 + 0) = 0; sliced off again), _linear then
+    _host_aggregate for host tensors."""
+    weight, bias = lin.weight, lin.bias
+    if a.dim() != 2 or a.shape[0] != graph.nnz or a.shape[1] != weight.shape[1]:
+        raise ValueError("GINEConv: edge features must be [nnz, edge_dim] = [%d, %d] in the graph's entry order, got %s"
+                         % (graph.nnz, weight.shape[1], tuple(a.shape)))
+    if a.dtype != h_src.dtype:
+        raise TypeError("GINEConv: node and edge features must have one dtype, got %s and %s" % (h_src.dtype, a.dtype))
+    if not h_src.is_cuda:
+        return _host_aggregate(graph, h_src, _linear(lin, a), "add", "relu")
+    width = h_src.shape[1]
+    pad = ops_edge.head_width_padded(width, h_src.dtype, pow2=False) - width
+    if pad:
+        h_src, weight = F.nn.functional.pad(h_src, (0, pad)), F.nn.functional.pad(weight, (0, 0, 0, pad))
+        bias = None if bias is None else F.nn.functional.pad(bias, (0, pad))
+    out = ops_efp.u_op_proj_e_sum(graph, h_src, a, weight, bias, "add", "relu")
+    return out[:, :width] if pad else out
+
+
 class GINEConv(F.nn.Module):
     """DGL's GINEConv.  forward(graph, node_feat, edge_feat) -> apply_func's output, [n_dst, F] without one; node_feat: a tensor
-    [n_src, F], or (feat_src, feat_dst) for blocks; edge_feat [nnz, F] in the graph's entry order."""
+    [n_src, F], or (feat_src, feat_dst) for blocks; edge_feat [nnz, F] in the graph's entry order -- with edge_dim: [nnz, edge_dim],
+    projected by the layer's own `lin` = Linear(edge_dim, in_feats) inside the aggregation kernel."""
 
-    def __init__(self, apply_func=None, init_eps=0, learn_eps=False):
+    def __init__(self, apply_func=None, init_eps=0, learn_eps=False, edge_dim=None, in_feats=None):
         super().__init__()
         self.apply_func = apply_func
+        if edge_dim is not None:
+            if in_feats is None:
+                raise ValueError("GINEConv: edge_dim needs in_feats, the node feature width that the edge attributes are projected to")
+            if not 1 <= int(edge_dim) <= ops_efp.MAX_DE:
+                raise ValueError("GINEConv: edge_dim must be in 1..%d, got %r (wider attributes: project them first)" % (ops_efp.MAX_DE, edge_dim))
+            self.lin = F.nn.Linear(int(edge_dim), int(in_feats))
         eps = F.tensor([float(init_eps)])
         if learn_eps:
             self.eps = F.nn.Parameter(eps)
@@ -69,8 +103,21 @@ class GINEConv(F.nn.Module):
     def forward(self, graph, node_feat, edge_feat):
         graph = as_csr_graph(graph)
         h_src, h_dst = _split_feat(graph, node_feat)
-        _check_edge_feat(graph, h_src, edge_feat, "GINEConv")
-        out = (1 + self.eps.to(h_dst.dtype)) * h_dst + _aggregate(graph, h_src, edge_feat, "add", "relu")
+        if getattr(self, "lin", None) is not None:
+            if h_src.shape[1] != self.lin.out_features:
+                raise ValueError("GINEConv: node features have %d columns, in_feats is %d" % (h_src.shape[1], self.lin.out_features))
+            agg = _aggregate_projected(graph, h_src, edge_feat, self.lin)
+        else:
+            _check_edge_feat(graph, h_src, edge_feat, "GINEConv")
+            agg = _aggregate(graph, h_src, edge_feat, "add", "relu")
+        out = (1 + self.eps.to(h_dst.dtype)) * h_dst + agg
+        return out if self.apply_func is None else self.apply_func(out)
+
+    def forward_projected(self, graph, node_feat, edge_attr, lin):
+        """forward with e_ij = lin(a_ij) formed inside the aggregation, for a caller that owns the Linear (GINE)."""
+        graph = as_csr_graph(graph)
+        h_src, h_dst = _split_feat(graph, node_feat)
+        out = (1 + self.eps.to(h_dst.dtype)) * h_dst + _aggregate_projected(graph, h_src, edge_attr, lin)
         return out if self.apply_func is None else self.apply_func(out)
 
     def extra_repr(self):
@@ -80,10 +127,15 @@ class GINEConv(F.nn.Module):
 class GINE(F.nn.Module):
     """n_layers of: e = enc_l(edge_attr); h = relu(lin_l(GINEConv_l(graph, h, e))), then logits = cls(h).  Every layer has its own
     Linear(edge_feat, width) encoder of the edge attributes (the width of that layer's input) and a learned eps.
-    forward(graph, x, edge_attr) -> logits [N, nclass]; edge_attr [nnz, edge_feat] in the graph's entry order."""
+    forward(graph, x, edge_attr) -> logits [N, nclass]; edge_attr [nnz, edge_feat] in the graph's entry order.  fused_edge=True
+    (edge_feat <= 16): e is not materialised -- each layer's aggregation forms it per entry from edge_attr and its encoder's weight
+    and bias.  The parameters and state_dict() keys do not depend on it: one state dict loads into both."""
 
-    def __init__(self, nfeat, edge_feat, nhid, nclass, n_layers=2):
+    def __init__(self, nfeat, edge_feat, nhid, nclass, n_layers=2, fused_edge=False):
         super().__init__()
+        if fused_edge and not 1 <= int(edge_feat) <= ops_efp.MAX_DE:
+            raise ValueError("GINE: fused_edge needs edge_feat in 1..%d, got %r" % (ops_efp.MAX_DE, edge_feat))
+        self.fused_edge = bool(fused_edge)
         widths = [nfeat] + [nhid] * (n_layers - 1)
         self.edge_encoders = F.nn.ModuleList([F.nn.Linear(edge_feat, w) for w in widths])
         self.convs = F.nn.ModuleList([GINEConv(None, 0, learn_eps=True) for _ in widths])
@@ -94,6 +146,9 @@ class GINE(F.nn.Module):
         graph = as_csr_graph(graph)
         h = x
         for enc, conv, lin in zip(self.edge_encoders, self.convs, self.lins):
-            e = _linear(enc, edge_attr).to(h.dtype)
-            h = F.nn.functional.relu(_linear(lin, conv(graph, h, e)))
+            if self.fused_edge:
+                agg = conv.forward_projected(graph, h, edge_attr.to(h.dtype), enc)
+            else:
+                agg = conv(graph, h, _linear(enc, edge_attr).to(h.dtype))
+            h = F.nn.functional.relu(_linear(lin, agg))
         return _linear(self.cls, h)

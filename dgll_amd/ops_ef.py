@@ -19,7 +19,8 @@ can be captured), fp32 accumulation.  There is no CPU implementation here: a CPU
 their own).
 
 Not built: max / min over the messages, edge features of another width than the node features' (project them first: nn.GINE
-does), a projection fused into the kernel, the partitioned (multi-GPU) path.
+does; ops_efp.u_op_proj_e_sum fuses a projection of up to 16 attribute columns into the kernel, so that e is never an array),
+the partitioned (multi-GPU) path.
 """
 import ctypes as C
 

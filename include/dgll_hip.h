@@ -1211,6 +1211,51 @@ typedef struct dgll_res_gated_desc {
 } dgll_res_gated_desc;
 int dgll_hip_res_gated_pass(void* stream, const dgll_res_gated_desc* d);
 
+/* ---- Edge-feature aggregation with the edge projection fused in (PyG's GINEConv(edge_dim=)): dgll_hip_edge_feat_pass's message with
+ * e_k formed per entry in registers from the raw edge attributes, so that no pass reads or writes an [nnz, F] array
+ * (csrc/edge_proj.hip).  Entry k of row i of A is the edge j = col[k] -> i and a[k, :] its De attributes, in A's entry order.  With
+ * weight [De, F] and bias [F] (or NULL: 0), both fp32 and contiguous, and op / scale as dgll_hip_edge_feat_pass (DGLL_EF_ADD,
+ * DGLL_EF_ADD_RELU, DGLL_EF_MUL):
+ *     e_k = bias + sum_d a[k, d] weight[d, :]       fp32, from bias, d ascending, one fused multiply-add per term: the same bits in
+ *                                                   every pass, so the relu of the forward and the gates of the backward agree
+ *     t_k = s_i dm/de grad_out[i]                   (never stored)
+ *   DGLL_EFP_FORWARD  rowptr / col = A.  out[i] = s_i sum_k m(x[col_k], e_k); reads x (gathered), a at slot k; writes out [n_rows, F].
+ *   DGLL_EFP_COLS     rowptr / col = A^T with perm (graph.transpose()).  grad_x[j] = sum_k' s_i dm/dx grad_out[i]; reads grad_out
+ *                     (gathered), scale (by the gathered row), x (held; ADD_RELU), a at slot perm[k']; writes grad_x [n_rows, F].
+ *                     ADD_RELU and MUL only: the grad_x of ADD reads neither x nor e and is dgll_hip_edge_feat_pass's DGLL_EF_COLS.
+ *   DGLL_EFP_PARAM    rowptr / col = A.  `partials` workgroups take the row tiles grid-stride; each writes one slab
+ *                     slabs[p] = [De + 1, F] fp32: rows d < De the workgroup's share of grad_weight[d] = sum_k a[k, d] t_k, row De
+ *                     that of grad_bias = sum_k t_k.  The caller sums the slabs in slab order.  Reads grad_out (held), a, x
+ *                     (gathered; ADD_RELU, MUL), weight and bias (ADD_RELU).  Every element of every slab is written.
+ *   DGLL_EFP_DOTS     rowptr / col = A.  grad_a[k, d] = sum over the columns of weight[d, :] t_k, in `dtype`; reads grad_out (held),
+ *                     weight, x (gathered; ADD_RELU, MUL), a and bias (ADD_RELU).  Past one column block (F > 64 lane vectors) the
+ *                     per-block partial dots go to dots_part [col_blocks, nnz, De] fp32 instead (required then; the caller sums them in
+ *                     block order) and grad_a is not written.  Columns of grad_a's pitch past De are not written.
+ * 1 <= De <= DGLL_EFP_MAX_DE.  a: `dtype`, pitch ld_a of whole 16-byte vectors >= De; the columns past De are never read into a
+ * result.  Operands a (pass, op) does not read may be NULL and are not dereferenced.  Everything else (dtype, pitches, F, column
+ * blocks, long rows, clamped col / perm, no atomics, nothing allocated, synchronised or read back, n_rows == 0) as
+ * dgll_hip_edge_feat_pass.                                                                                                          */
+enum { DGLL_EFP_FORWARD = 0, DGLL_EFP_COLS = 1, DGLL_EFP_PARAM = 2, DGLL_EFP_DOTS = 3 };
+#define DGLL_EFP_LONG_ROW 256
+#define DGLL_EFP_MAX_DE 16
+#define DGLL_EFP_MAX_PARTIALS 512
+typedef struct dgll_edge_proj_desc {
+    int pass; int dtype; int op; int De;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int64_t F;
+    const float* scale;
+    const void* x; int64_t ld_x;
+    const void* a; int64_t ld_a;
+    const float* weight; const float* bias;
+    const void* grad_out; int64_t ld_grad_out;
+    void* out; int64_t ld_out;
+    void* grad_x; int64_t ld_grad_x;
+    void* grad_a; int64_t ld_grad_a;
+    float* dots_part;
+    float* slabs; int64_t partials;
+} dgll_edge_proj_desc;
+int dgll_hip_edge_proj_pass(void* stream, const dgll_edge_proj_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
