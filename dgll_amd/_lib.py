@@ -221,6 +221,25 @@ EFP_MAX_DE = 16             # DGLL_EFP_MAX_DE: the widest edge attribute row
 EFP_MAX_PARTIALS = 512      # DGLL_EFP_MAX_PARTIALS: workgroups (and slabs) of the PARAM pass at the most
 
 
+class GmmDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_gmm_desc (dgll_hip_gmm_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int), ("K", C.c_int), ("dim", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("F", C.c_int64), ("scale", C.c_void_p),
+                ("pseudo", C.c_void_p), ("ld_pseudo", C.c_int64), ("mu", C.c_void_p), ("inv_sigma", C.c_void_p),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("dz", C.c_void_p), ("ld_dz", C.c_int64),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("p", C.c_void_p), ("ld_p", C.c_int64),
+                ("grad_pseudo", C.c_void_p), ("ld_grad_pseudo", C.c_int64), ("slabs", C.c_void_p), ("partials", C.c_int64)]
+
+
+GMM_EXPAND, GMM_CONTRACT, GMM_PARAM = 0, 1, 2
+GMM_LONG_ROW = 256          # DGLL_GMM_LONG_ROW of include/dgll_hip.h
+GMM_MAX_DIM = 8             # DGLL_GMM_MAX_DIM: pseudo-coordinates of an entry at the most
+GMM_MAX_KERNELS = 64        # DGLL_GMM_MAX_KERNELS: Gaussian kernels at the most
+GMM_KERNEL_BLOCK = 8        # DGLL_GMM_KERNEL_BLOCK: kernels a launch block of EXPAND accumulates at the most
+GMM_MAX_PARTIALS = 2048     # DGLL_GMM_MAX_PARTIALS: workgroups (and slabs) of the PARAM pass at the most
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -372,6 +391,7 @@ SIGNATURES = {
     "dgll_hip_gated_pass": (_i32, [_vp, C.POINTER(GatedDesc)]),
     "dgll_hip_res_gated_pass": (_i32, [_vp, C.POINTER(ResGatedDesc)]),
     "dgll_hip_edge_proj_pass": (_i32, [_vp, C.POINTER(EdgeProjDesc)]),
+    "dgll_hip_gmm_pass": (_i32, [_vp, C.POINTER(GmmDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

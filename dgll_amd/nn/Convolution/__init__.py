@@ -15,9 +15,10 @@ from .gineconv import GINEConv, GINE
 from .cfconv import CFConv, ShiftedSoftplus
 from .gatedgcnconv import GatedGCNConv, GatedGCN
 from .resgatedconv import ResGatedGraphConv, ResGatedGCN
+from .gmmconv import GMMConv, MoNet, degree_pseudo
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
            "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN",
            "PNAConv", "PNA", "GINEConv", "GINE", "CFConv", "ShiftedSoftplus", "GatedGCNConv", "GatedGCN",
-           "ResGatedGraphConv", "ResGatedGCN"]
+           "ResGatedGraphConv", "ResGatedGCN", "GMMConv", "MoNet", "degree_pseudo"]

@@ -1256,6 +1256,55 @@ typedef struct dgll_edge_proj_desc {
 } dgll_edge_proj_desc;
 int dgll_hip_edge_proj_pass(void* stream, const dgll_edge_proj_desc* d);
 
+/* ---- Gaussian-mixture edge weights (MoNet / DGL's GMMConv): three passes behind one entry point (csrc/gmm.hip) -------------------------
+ * Every entry e of a CSR matrix A [n_dst x n_src] (rectangular allowed, duplicate entries are separate edges) carries `dim`
+ * pseudo-coordinates pseudo[e, :] (fp32, pitch ld_pseudo >= dim in elements, 4-byte alignment is enough), in A's entry order.  With
+ * mu and inv_sigma fp32 [K, dim], contiguous:
+ *     w_k(e) = exp(-0.5 * sum_d ((pseudo[e, d] - mu[k, d]) * inv_sigma[k, d])^2)      fp32, d ascending, ONE device function in every
+ *                                                                                      pass: u == mu gives exactly 1, an exponent
+ *                                                                                      below 2^-149 exactly 0
+ *     Z[i, k, :] = scale[i] * sum_{e = (j -> i)} w_k(e) * X[j, :]                      Z: [n_dst, K * F], kernel-major blocks of width F
+ *   DGLL_GMM_EXPAND    rowptr / col = A, n_rows = n_dst, n_cols = n_src.  Reads x [n_src, F] (gathered once per entry into up to
+ *                      DGLL_GMM_KERNEL_BLOCK kernels' accumulators; more kernels re-gather x once per block), pseudo at slot e, scale
+ *                      (fp32 [n_rows], or NULL: 1); writes out = Z [n_rows, K * F] of `dtype` (zeros for an empty row).
+ *   DGLL_GMM_CONTRACT  rowptr / col = A^T with perm (graph.transpose(): A^T's entry -> A's entry), n_rows = n_src, n_cols = n_dst.
+ *                      Reads dz [n_dst, K * F] (gathered), pseudo at slot perm[e']; writes out = dX [n_src, F]:
+ *                      dX[j] = sum_e sum_k w_k(e) dz[i_e, k, :] (zeros for a source no row references).  scale is not read: the
+ *                      caller scales the rows of dz.
+ *   DGLL_GMM_PARAM     no rowptr, no col: the nnz entries are streamed.  Reads p fp32 [nnz, ld_p], ld_p = K rounded up to 4, 16-byte
+ *                      aligned (p[e, k] = <x[j_e], dz[i_e, k, :]>: dgll_hip_typed_spmm_pass's DGLL_TYPED_EDGE_DOTS with B = K), and
+ *                      pseudo.  With u = pseudo[e], s = inv_sigma: writes grad_pseudo[e, d] = sum_k p_k w_k * (-(u_d - mu_kd) s_kd^2)
+ *                      (fp32 [nnz, ld_grad_pseudo], or NULL: not wanted) and one fp32 slab [2, K, dim] per workgroup, `partials`
+ *                      workgroups taking the entries grid-stride: slabs[w, 0] the share of grad_mu = sum_e p_k w_k (u_d - mu_kd) s_kd^2,
+ *                      slabs[w, 1] that of grad_inv_sigma = -sum_e p_k w_k (u_d - mu_kd)^2 s_kd.  Every element of every slab is
+ *                      written; the caller sums the slabs in slab order.  dtype is checked and otherwise unused.
+ * 1 <= dim <= DGLL_GMM_MAX_DIM, 1 <= K <= DGLL_GMM_MAX_KERNELS; mu and inv_sigma are staged in LDS once per workgroup.  Matrices of
+ * `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation), pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned bases; F a
+ * multiple of the vector width.  Rows wider than 64 lane vectors are cut into column blocks; rows longer than DGLL_GMM_LONG_ROW
+ * entries are swept by a whole workgroup.  col and perm values used for addressing are clamped.  No atomics: two runs give the same
+ * bits.  No pass allocates, synchronises or reads anything back: the calls can be captured into a graph.                           */
+enum { DGLL_GMM_EXPAND = 0, DGLL_GMM_CONTRACT = 1, DGLL_GMM_PARAM = 2 };
+#define DGLL_GMM_LONG_ROW 256
+#define DGLL_GMM_MAX_DIM 8
+#define DGLL_GMM_MAX_KERNELS 64
+#define DGLL_GMM_KERNEL_BLOCK 8
+#define DGLL_GMM_MAX_PARTIALS 2048
+typedef struct dgll_gmm_desc {
+    int pass; int dtype; int K; int dim;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int64_t F;
+    const float* scale;
+    const float* pseudo; int64_t ld_pseudo;
+    const float* mu; const float* inv_sigma;
+    const void* x; int64_t ld_x;
+    const void* dz; int64_t ld_dz;
+    void* out; int64_t ld_out;
+    const float* p; int64_t ld_p;
+    float* grad_pseudo; int64_t ld_grad_pseudo;
+    float* slabs; int64_t partials;
+} dgll_gmm_desc;
+int dgll_hip_gmm_pass(void* stream, const dgll_gmm_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
