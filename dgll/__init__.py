@@ -28,6 +28,7 @@ _ALIASES = {
     "dgll.nn.Convolution.gatedgcnconv": "dgll_amd.nn.Convolution.gatedgcnconv",
     "dgll.nn.Convolution.resgatedconv": "dgll_amd.nn.Convolution.resgatedconv",
     "dgll.nn.Convolution.gmmconv": "dgll_amd.nn.Convolution.gmmconv",
+    "dgll.nn.Convolution.genconv": "dgll_amd.nn.Convolution.genconv",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",

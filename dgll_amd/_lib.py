@@ -240,6 +240,24 @@ GMM_KERNEL_BLOCK = 8        # DGLL_GMM_KERNEL_BLOCK: kernels a launch block of E
 GMM_MAX_PARTIALS = 2048     # DGLL_GMM_MAX_PARTIALS: workgroups (and slabs) of the PARAM pass at the most
 
 
+class SoftAggDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_soft_agg_desc (dgll_hip_soft_agg_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int), ("mode", C.c_int), ("semi_grad", C.c_int),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("perm", C.c_void_p), ("n_rows", C.c_int64), ("n_cols", C.c_int64),
+                ("nnz", C.c_int64), ("F", C.c_int64), ("eps", C.c_float), ("theta", C.c_void_p),
+                ("x", C.c_void_p), ("ld_x", C.c_int64), ("e", C.c_void_p), ("ld_e", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("out", C.c_void_p), ("ld_out", C.c_int64),
+                ("stats", C.c_void_p), ("ld_stats", C.c_int64),
+                ("grad_x", C.c_void_p), ("ld_grad_x", C.c_int64), ("grad_e", C.c_void_p), ("ld_grad_e", C.c_int64),
+                ("partials", C.c_void_p), ("n_partials", C.c_int64), ("grad_theta", C.c_void_p)]
+
+
+SOFT_AGG_FORWARD, SOFT_AGG_ROWS, SOFT_AGG_COLS = 0, 1, 2
+SOFT_AGG_SOFTMAX, SOFT_AGG_POWER = 0, 1
+SOFT_AGG_LONG_ROW = 256         # DGLL_SOFT_AGG_LONG_ROW of include/dgll_hip.h
+SOFT_AGG_MAX_PARTIALS = 1024    # DGLL_SOFT_AGG_MAX_PARTIALS: workgroups per column block (and partials) of the ROWS pass at the most
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -392,6 +410,7 @@ SIGNATURES = {
     "dgll_hip_res_gated_pass": (_i32, [_vp, C.POINTER(ResGatedDesc)]),
     "dgll_hip_edge_proj_pass": (_i32, [_vp, C.POINTER(EdgeProjDesc)]),
     "dgll_hip_gmm_pass": (_i32, [_vp, C.POINTER(GmmDesc)]),
+    "dgll_hip_soft_agg_pass": (_i32, [_vp, C.POINTER(SoftAggDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1305,6 +1305,62 @@ typedef struct dgll_gmm_desc {
 } dgll_gmm_desc;
 int dgll_hip_gmm_pass(void* stream, const dgll_gmm_desc* d);
 
+/* ---- Per-column soft aggregation (DeeperGCN: PyG's GENConv, SoftmaxAggregation, PowerMeanAggregation) and its exact backward; three
+ * passes behind one entry point (csrc/soft_agg.hip).  Entry k of row i of A (rowptr / col, [n_dst x n_src], rectangular allowed, edge
+ * values are not read) is the edge j = col[k] -> i and e[k] its row (optional: e == NULL reads none, in every pass); duplicate entries
+ * are separate edges.  For every column independently, with theta = *theta (t or p: ONE fp32 value in device memory, read by the
+ * kernels and never by the host), x [n_src, F], e [nnz, F] and g = grad_out [n_dst, F]:
+ *     m_k = relu(x[j] + e[k]) + eps        gate_k = (x[j] + e[k] > 0)      the fp32 sum of the two STORED values, ONE device function
+ *                                                                          in every pass: relu and gates agree bit for bit
+ *   DGLL_SOFT_AGG_SOFTMAX   a_k = exp(t m_k - lse_i), lse_i = log sum_k exp(t m_k), out_i = sum_k a_k m_k      (online, exp2 form, one
+ *                           running maximum PER COLUMN)
+ *                           d out_i / d m_k = a_k (1 + t (m_k - out_i))      (semi_grad != 0: a_k alone)
+ *                           d out_i / d t   = sum_k a_k (m_k^2 - out_i^2)
+ *   DGLL_SOFT_AGG_POWER     mc_k = min(m_k, 100), S_i = sum_k mc_k^p, out_i = (S_i / deg_i)^(1/p)      (powers as exp2(p log2 mc))
+ *                           d out_i / d m_k = (out_i / S_i) mc_k^(p-1)       (0 where m_k > 100)
+ *                           d out_i / d p   = (out_i / p) sum_k (mc_k^p / S_i) (ln mc_k - ln out_i)
+ *   DGLL_SOFT_AGG_FORWARD  rowptr / col = A (n_rows = n_dst, n_cols = n_src).  Reads x (gathered), e at slot k; writes out [n_rows, F] of
+ *                          `dtype` and the fp32 row statistics stats [n_rows, 2 F]: SOFTMAX {lse | out}, POWER {out | S}, the unrounded
+ *                          values.  A row without entries: zeros in both.  Nothing per edge is written.
+ *   DGLL_SOFT_AGG_ROWS     rowptr / col = A.  Reads grad_out and stats (held), x (gathered), e at slot k.  Writes, when grad_e is
+ *                          non-NULL (e is then required), grad_e[k] = g_i (d out_i / d m_k) gate_k: one store per entry, no reduction;
+ *                          and, when grad_theta is non-NULL, the scalar gradient sum over rows and columns of g (d out / d theta):
+ *                          at most n_partials workgroups take the row tiles grid-stride, each reduces its lanes in a fixed order into
+ *                          ONE fp32 of partials (n_partials * ceil(F / 64 vectors) floats, required then), and a second small kernel
+ *                          sums the partials in workgroup order into grad_theta[0].  At least one of the two.  SOFTMAX with semi_grad
+ *                          has no scalar gradient: grad_theta must be NULL.
+ *   DGLL_SOFT_AGG_COLS     rowptr / col = A^T with perm, A^T's entry k' -> A's entry (graph.transpose(); n_rows = n_src, n_cols = n_dst;
+ *                          perm is required when e is given).  Reads x (held), grad_out and stats (gathered at i = col[k']), e at slot
+ *                          perm[k']; writes grad_x [n_rows, F] (zeros for a source no row references).
+ * eps >= 0.  Operands a pass does not read may be NULL and are not dereferenced.  nnz: the rows of e / grad_e (perm values are clamped
+ * to [0, nnz), col values used for addressing to [0, n_cols)).  Matrices of `dtype` (DGLL_F32 / DGLL_BF16, fp32 accumulation) but for
+ * the fp32 stats; pitches ld_* in elements, each its own: whole 16-byte vectors >= F (stats: >= 2 F), 16-byte aligned bases; columns
+ * behind F are never read into a result and never written.  F a positive multiple of the vector width (4 fp32 / 8 bf16 columns);
+ * widths past 64 vectors go to column blocks.  Rows longer than DGLL_SOFT_AGG_LONG_ROW entries are swept by a whole workgroup and,
+ * where there is a row reduction, merged through LDS in group order (SOFTMAX: with a per-column rescale).  No atomics: two runs give
+ * the same bits, grad_theta included.  No pass allocates, synchronises or reads anything back: the calls can be captured into a
+ * graph.  n_rows == 0 launches nothing and writes nothing, grad_theta included.                                                      */
+enum { DGLL_SOFT_AGG_FORWARD = 0, DGLL_SOFT_AGG_ROWS = 1, DGLL_SOFT_AGG_COLS = 2 };
+enum { DGLL_SOFT_AGG_SOFTMAX = 0, DGLL_SOFT_AGG_POWER = 1 };
+#define DGLL_SOFT_AGG_LONG_ROW 256
+#define DGLL_SOFT_AGG_MAX_PARTIALS 1024
+typedef struct dgll_soft_agg_desc {
+    int pass; int dtype; int mode; int semi_grad;
+    const int64_t* rowptr; const int32_t* col; const int64_t* perm; int64_t n_rows; int64_t n_cols; int64_t nnz;
+    int64_t F; float eps;
+    const float* theta;
+    const void* x; int64_t ld_x;
+    const void* e; int64_t ld_e;
+    const void* grad_out; int64_t ld_grad_out;
+    void* out; int64_t ld_out;
+    float* stats; int64_t ld_stats;
+    void* grad_x; int64_t ld_grad_x;
+    void* grad_e; int64_t ld_grad_e;
+    float* partials; int64_t n_partials;
+    float* grad_theta;
+} dgll_soft_agg_desc;
+int dgll_hip_soft_agg_pass(void* stream, const dgll_soft_agg_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
