@@ -125,9 +125,13 @@ def _against_reference(graph, F, dtype, aggs, scalers, delta, with_y, label, see
 
 @pytest.mark.parametrize("F,dtype", [(8, torch.float32), (20, torch.float32), (64, torch.float32), (256, torch.float32), (320, torch.float32),
                                      (8, torch.bfloat16), (24, torch.bfloat16), (64, torch.bfloat16), (512, torch.bfloat16),
-                                     (520, torch.bfloat16)], ids=lambda v: str(v).replace("torch.", ""))
+                                     (520, torch.bfloat16),
+                                     (72, torch.float32), (128, torch.float32),                             # 32 lanes a row: idle lanes, full
+                                     (72, torch.bfloat16), (136, torch.bfloat16), (256, torch.bfloat16)],   # 16 lanes; 32: idle lanes, full
+                         ids=lambda v: str(v).replace("torch.", ""))
 def test_default_aggregators_on_rmat(rmat, F, dtype):
-    """idle lanes, a vector count that is no power of two, one full row of lanes, exactly one and more than one column block"""
+    """idle lanes, a vector count that is no power of two, one full row of lanes, exactly one and more than one column block; every
+    lane width (8, 16, 32, 64 lanes a row) in both dtypes"""
     _against_reference(rmat, F, dtype, DEFAULT_AGGS, DEFAULT_SCALERS, 1.3, True, "rmat F=%d" % F, 100 + F)
 
 

@@ -106,7 +106,9 @@ def _check(got, want, dtype, label="", names=NAMES, bf16_bars=None):
 
 
 CASES = [(8, 1, 1, torch.float32), (40, 2, 3, torch.float32), (64, 4, 16, torch.float32), (256, 8, 16, torch.float32), (512, 2, 4, torch.float32),
-         (48, 3, 5, torch.bfloat16), (64, 5, 50, torch.bfloat16), (256, 4, 16, torch.bfloat16), (64, 32, 40, torch.bfloat16)]
+         (48, 3, 5, torch.bfloat16), (64, 5, 50, torch.bfloat16), (256, 4, 16, torch.bfloat16), (64, 32, 40, torch.bfloat16),
+         (72, 2, 3, torch.float32), (128, 4, 16, torch.float32),        # 32 lanes a row in fp32: with idle lanes, full
+         (72, 3, 5, torch.bfloat16)]                                    # 16 lanes a row with idle lanes
 
 
 @pytest.mark.parametrize("with_norm", [True, False], ids=["norm", "nonorm"])
