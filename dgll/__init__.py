@@ -29,6 +29,8 @@ _ALIASES = {
     "dgll.nn.Convolution.resgatedconv": "dgll_amd.nn.Convolution.resgatedconv",
     "dgll.nn.Convolution.gmmconv": "dgll_amd.nn.Convolution.gmmconv",
     "dgll.nn.Convolution.genconv": "dgll_amd.nn.Convolution.genconv",
+    "dgll.nn.Convolution.edgeconv": "dgll_amd.nn.Convolution.edgeconv",
+    "dgll.knn": "dgll_amd.knn",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",
@@ -49,5 +51,6 @@ for _alias, _target in _ALIASES.items():
     sys.modules[_alias] = importlib.import_module(_target)
 nn = sys.modules["dgll.nn"]
 community = sys.modules["dgll.community"]
+knn = sys.modules["dgll.knn"]
 embedding = sys.modules["dgll.embedding"]      # `import dgll.embedding` finds the alias in sys.modules and binds no attribute itself
 __version__ = dgll_amd.__version__

@@ -256,6 +256,8 @@ SOFT_AGG_FORWARD, SOFT_AGG_ROWS, SOFT_AGG_COLS = 0, 1, 2
 SOFT_AGG_SOFTMAX, SOFT_AGG_POWER = 0, 1
 SOFT_AGG_LONG_ROW = 256         # DGLL_SOFT_AGG_LONG_ROW of include/dgll_hip.h
 SOFT_AGG_MAX_PARTIALS = 1024    # DGLL_SOFT_AGG_MAX_PARTIALS: workgroups per column block (and partials) of the ROWS pass at the most
+KNN_MAX_K, KNN_MAX_D = 64, 256              # DGLL_KNN_MAX_K, DGLL_KNN_MAX_D: the limits of dgll_hip_knn
+KNN_QUERY_TILE, KNN_CAND_TILE = 256, 32     # DGLL_KNN_QUERY_TILE, DGLL_KNN_CAND_TILE: its tile geometry
 
 
 class DgllHipError(RuntimeError):
@@ -411,6 +413,7 @@ SIGNATURES = {
     "dgll_hip_edge_proj_pass": (_i32, [_vp, C.POINTER(EdgeProjDesc)]),
     "dgll_hip_gmm_pass": (_i32, [_vp, C.POINTER(GmmDesc)]),
     "dgll_hip_soft_agg_pass": (_i32, [_vp, C.POINTER(SoftAggDesc)]),
+    "dgll_hip_knn": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -17,9 +17,12 @@ from .gatedgcnconv import GatedGCNConv, GatedGCN
 from .resgatedconv import ResGatedGraphConv, ResGatedGCN
 from .gmmconv import GMMConv, MoNet, degree_pseudo
 from .genconv import GENConv, DeeperGCN
+from .edgeconv import EdgeConv, DGCNN
+from ...knn import KNNGraph, SegmentedKNNGraph
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
            "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN",
            "PNAConv", "PNA", "GINEConv", "GINE", "CFConv", "ShiftedSoftplus", "GatedGCNConv", "GatedGCN",
-           "ResGatedGraphConv", "ResGatedGCN", "GMMConv", "MoNet", "degree_pseudo", "GENConv", "DeeperGCN"]
+           "ResGatedGraphConv", "ResGatedGCN", "GMMConv", "MoNet", "degree_pseudo", "GENConv", "DeeperGCN",
+           "EdgeConv", "DGCNN", "KNNGraph", "SegmentedKNNGraph"]

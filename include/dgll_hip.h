@@ -1361,6 +1361,33 @@ typedef struct dgll_soft_agg_desc {
 } dgll_soft_agg_desc;
 int dgll_hip_soft_agg_pass(void* stream, const dgll_soft_agg_desc* d);
 
+/* ---- Exact k nearest neighbours inside segments (DGL's knn_graph / segmented_knn_graph; the graph of Dynamic Graph CNN), one launch
+ * (csrc/knn.hip).
+ *   Inputs    x [n, D] of `dtype` (DGLL_F32 / DGLL_BF16) on a row pitch ld_x >= D in elements; whatever lies behind column D of a row
+ *             is never read into a result.  16-byte loads are used when x is 16-byte aligned and the pitch a whole number of 16-byte
+ *             vectors (the row's pitch is then addressable up to the end of the vector that holds column D - 1), scalar loads otherwise.
+ *             seg_ptr int64 [n_segs + 1], ascending, cuts the rows into n_segs contiguous segments; empty segments are allowed; a row
+ *             that no segment covers gets no entries.  k >= 1; exclude_self is a flag.
+ *   Distance  d(i, j) = sum over c = 0 .. D-1 of (x[i,c] - x[j,c])^2 in fp32, on the inputs converted exactly to fp32: the DIFFERENCE
+ *             form (never |xi|^2 - 2 xi.xj + |xj|^2, whose cancellation changes which neighbour wins).  A NaN distance sorts as +inf.
+ *   Output    row i of segment s gets deg_i = min(k, size(s) - (exclude_self ? 1 : 0)) entries, written at out_rowptr[i] (int64 [n + 1],
+ *             an INPUT: the caller knows deg_i from the segment sizes): the deg_i candidates j of its own segment with the smallest
+ *             (d, j) in lexicographic order, in that order -- among equal fp32 distances the smaller index wins.  With exclude_self the
+ *             candidate j == i is skipped by INDEX, not by distance: a duplicate point is still a neighbour.  out_col int32 [out_nnz]
+ *             receives global row ids, out_dist fp32 [out_nnz] (may be NULL) the distances; a slot outside [0, out_nnz) is not written.
+ *   Limits    1 <= k <= DGLL_KNN_MAX_K, 1 <= D <= DGLL_KNN_MAX_D, n < 2^31; anything else returns DGLL_ERR_INVALID and names the limit.
+ *             Every argument check happens on the host before any launch.
+ * Workgroups take tiles of DGLL_KNN_QUERY_TILE consecutive rows (one lane per query) and stream the segment's rows through LDS in tiles of
+ * DGLL_KNN_CAND_TILE rows.  No atomics, no scratch memory, nothing of size n x n or n x segment anywhere: two runs give the same bits.
+ * Nothing is allocated, synchronised or read back: the call can be captured into a graph.  n == 0, n_segs == 0 or out_nnz == 0 launch
+ * nothing.                                                                                                                            */
+#define DGLL_KNN_MAX_K 64
+#define DGLL_KNN_MAX_D 256
+#define DGLL_KNN_QUERY_TILE 256
+#define DGLL_KNN_CAND_TILE 32
+int dgll_hip_knn(void* stream, const void* x, int64_t ld_x, int dtype, int64_t n, int64_t D, const int64_t* seg_ptr, int64_t n_segs,
+                 int k, int exclude_self, const int64_t* out_rowptr, int32_t* out_col, float* out_dist, int64_t out_nnz);
+
 #ifdef __cplusplus
 }
 #endif
