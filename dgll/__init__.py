@@ -30,7 +30,9 @@ _ALIASES = {
     "dgll.nn.Convolution.gmmconv": "dgll_amd.nn.Convolution.gmmconv",
     "dgll.nn.Convolution.genconv": "dgll_amd.nn.Convolution.genconv",
     "dgll.nn.Convolution.edgeconv": "dgll_amd.nn.Convolution.edgeconv",
+    "dgll.nn.Convolution.pointnetconv": "dgll_amd.nn.Convolution.pointnetconv",
     "dgll.knn": "dgll_amd.knn",
+    "dgll.points": "dgll_amd.points",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
     "dgll.data": "dgll_amd.data",
@@ -52,5 +54,6 @@ for _alias, _target in _ALIASES.items():
 nn = sys.modules["dgll.nn"]
 community = sys.modules["dgll.community"]
 knn = sys.modules["dgll.knn"]
+points = sys.modules["dgll.points"]
 embedding = sys.modules["dgll.embedding"]      # `import dgll.embedding` finds the alias in sys.modules and binds no attribute itself
 __version__ = dgll_amd.__version__

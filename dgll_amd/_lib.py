@@ -258,6 +258,8 @@ SOFT_AGG_LONG_ROW = 256         # DGLL_SOFT_AGG_LONG_ROW of include/dgll_hip.h
 SOFT_AGG_MAX_PARTIALS = 1024    # DGLL_SOFT_AGG_MAX_PARTIALS: workgroups per column block (and partials) of the ROWS pass at the most
 KNN_MAX_K, KNN_MAX_D = 64, 256              # DGLL_KNN_MAX_K, DGLL_KNN_MAX_D: the limits of dgll_hip_knn
 KNN_QUERY_TILE, KNN_CAND_TILE = 256, 32     # DGLL_KNN_QUERY_TILE, DGLL_KNN_CAND_TILE: its tile geometry
+FPS_MAX_D, FPS_MAX_REG_SEG = 32, 8192       # DGLL_FPS_MAX_D, DGLL_FPS_MAX_REG_SEG: dgll_hip_fps keeps dmin in registers up to that segment size
+RADIUS_MAX_K, RADIUS_MAX_D = 64, 32         # DGLL_RADIUS_MAX_K, DGLL_RADIUS_MAX_D: the limits of dgll_hip_radius
 
 
 class DgllHipError(RuntimeError):
@@ -414,6 +416,9 @@ SIGNATURES = {
     "dgll_hip_gmm_pass": (_i32, [_vp, C.POINTER(GmmDesc)]),
     "dgll_hip_soft_agg_pass": (_i32, [_vp, C.POINTER(SoftAggDesc)]),
     "dgll_hip_knn": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
+    "dgll_hip_fps": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "dgll_hip_radius": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _i64, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp,
+                               _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

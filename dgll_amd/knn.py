@@ -22,7 +22,8 @@ graph (the tables of the 64 most recent shapes are kept; a captured call goes on
 every graph it returned keeps alive).  UNEQUAL segments read `segs` on the host once per call (a tensor on the device synchronises) and upload two small tables.
 There is no CPU implementation: a CPU tensor raises.
 
-Not built: k > 64, D > 256, approximate search, knn(x, y) between two point sets, radius graphs.
+Not built: k > 64, D > 256, approximate search, knn(x, y) between two point sets.  Radius graphs, also between two point
+sets, are dgll_amd.points.radius / radius_graph.
 """
 import torch
 

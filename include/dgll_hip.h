@@ -1388,6 +1388,53 @@ int dgll_hip_soft_agg_pass(void* stream, const dgll_soft_agg_desc* d);
 int dgll_hip_knn(void* stream, const void* x, int64_t ld_x, int dtype, int64_t n, int64_t D, const int64_t* seg_ptr, int64_t n_segs,
                  int k, int exclude_self, const int64_t* out_rowptr, int32_t* out_col, float* out_dist, int64_t out_nnz);
 
+/* ---- Farthest point sampling inside segments (DGL's farthest_point_sampler, PyG's fps; the centroids of PointNet++), one launch
+ * (csrc/fps.hip).
+ *   Inputs    x [n, D] of `dtype` (DGLL_F32 / DGLL_BF16) on a row pitch ld_x >= D in elements; nothing behind column D of a row reaches
+ *             a result (16-byte loads under the rule of dgll_hip_knn).  seg_ptr int64 [n_segs + 1] cuts the rows into contiguous
+ *             segments, empty ones allowed.  max_seg: no segment is larger (the host knows the sizes; it chooses the kernel instance).
+ *   Samples   out_ptr int64 [n_segs + 1]: segment s yields m_s = out_ptr[s + 1] - out_ptr[s] samples, 0 <= m_s <= size_s (a larger
+ *             m_s is cut to size_s), written to out_idx int64 [n_out] (global row ids) at out_ptr[s]; a slot outside [0, n_out) is not
+ *             written.  start int64 [n_segs] or NULL: the offset inside the segment of sample 0 (NULL: 0; an offset outside the
+ *             segment is reduced modulo its size).  Sample t + 1 is the point not yet chosen with the largest
+ *             dmin_t(j) = min over the chosen c of d(j, c), d = sum_c (x[j, c] - x[c, c])^2 in fp32 on the inputs converted exactly to
+ *             fp32, columns ascending, each step a fused multiply-add (the difference form of dgll_hip_knn).  Among equal dmin the
+ *             smaller index wins.  A chosen point is never chosen again (its dmin becomes -inf): a segment of identical points yields
+ *             start, then the other indices ascending; m_s == size_s yields a permutation.  A NaN distance counts as 0.
+ *   out_dmin  fp32 [n_out] or NULL: the dmin each sample had when it was chosen (the coverage radius squared), +inf for sample 0.
+ *   scratch   fp32 [n], needed (non-NULL) only when max_seg > DGLL_FPS_MAX_REG_SEG; its contents before and after mean nothing.
+ *   Limits    1 <= D <= DGLL_FPS_MAX_D, n < 2^31; anything else returns DGLL_ERR_INVALID and names the limit, on the host before any launch.
+ * One workgroup per segment runs all of its samples, dmin in registers up to DGLL_FPS_MAX_REG_SEG points (in `scratch` above that,
+ * correct but slow: one workgroup still owns the segment).  No atomics, no grid-wide synchronisation, no workgroup waits for another:
+ * two runs give the same bits.  Nothing is allocated, synchronised or read back: the call can be captured into a graph.             */
+#define DGLL_FPS_MAX_D 32
+#define DGLL_FPS_MAX_REG_SEG 8192
+int dgll_hip_fps(void* stream, const void* x, int64_t ld_x, int dtype, int64_t n, int64_t D, const int64_t* seg_ptr, int64_t n_segs,
+                 int64_t max_seg, const int64_t* out_ptr, const int64_t* start, int64_t* out_idx, float* out_dmin, int64_t n_out,
+                 float* scratch);
+
+/* ---- Fixed-radius neighbours between two segmented point sets (PyG's radius / radius_graph, PointNet++'s ball query), three launches
+ * (csrc/radius.hip).
+ *   Inputs    queries y [m, D] with y_seg_ptr int64 [n_segs + 1], candidates x [n, D] with x_seg_ptr int64 [n_segs + 1]: query segment s
+ *             searches candidate segment s.  Both of `dtype`, each on its own pitch (ld >= D; 16-byte loads when both allow them).
+ *   Result    row i lists the candidates j of its segment with d(i, j) <= r2 (d as in dgll_hip_fps; a NaN distance sorts as +inf),
+ *             in ascending j, at most K of them: the K SMALLEST INDICES, PointNet++'s ball-query order.  exclude_self skips j == i by
+ *             global index (meaningful only when y is x).
+ *   Outputs   out_rowptr int64 [m + 1]; out_col int32 of capacity m K, the first nnz valid; out_dist fp32 of capacity m K or NULL;
+ *             out_nnz int64 [1] on the device.
+ *   scratch   int32 [m K + m]: the padded rows and the per-row counts.
+ *   Limits    1 <= K <= DGLL_RADIUS_MAX_K, 1 <= D <= DGLL_RADIUS_MAX_D, n, m < 2^31; anything else returns DGLL_ERR_INVALID and names
+ *             the limit, on the host before any launch.
+ * Search (tiles of DGLL_RADIUS_QUERY_TILE queries, one lane each, candidates through LDS DGLL_RADIUS_CAND_TILE rows at a time; a
+ * workgroup leaves a segment once all of its lanes hold K), a one-workgroup scan, a compaction.  No atomics: two runs give the same bits. */
+#define DGLL_RADIUS_MAX_K 64
+#define DGLL_RADIUS_MAX_D 32
+#define DGLL_RADIUS_QUERY_TILE 256
+#define DGLL_RADIUS_CAND_TILE 32
+int dgll_hip_radius(void* stream, const void* y, int64_t ld_y, int64_t m, const int64_t* y_seg_ptr, const void* x, int64_t ld_x, int64_t n,
+                    const int64_t* x_seg_ptr, int64_t n_segs, int dtype, int64_t D, float r2, int K, int exclude_self,
+                    int64_t* out_rowptr, int32_t* out_col, float* out_dist, int64_t* out_nnz, int32_t* scratch);
+
 #ifdef __cplusplus
 }
 #endif
