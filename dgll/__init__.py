@@ -31,6 +31,7 @@ _ALIASES = {
     "dgll.nn.Convolution.genconv": "dgll_amd.nn.Convolution.genconv",
     "dgll.nn.Convolution.edgeconv": "dgll_amd.nn.Convolution.edgeconv",
     "dgll.nn.Convolution.pointnetconv": "dgll_amd.nn.Convolution.pointnetconv",
+    "dgll.nn.Convolution.typedlinear": "dgll_amd.nn.Convolution.typedlinear",
     "dgll.knn": "dgll_amd.knn",
     "dgll.points": "dgll_amd.points",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",

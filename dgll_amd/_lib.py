@@ -419,6 +419,13 @@ SIGNATURES = {
     "dgll_hip_fps": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "dgll_hip_radius": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _i64, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp,
                                _vp]),
+    "dgll_hip_segment_mm_packed_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "dgll_hip_segment_mm_pack": (_i32, [_vp, _vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "dgll_hip_segment_mm_workspace": (_i64, [_i64]),
+    "dgll_hip_segment_mm": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _i32, _vp, _i64]),
+    "dgll_hip_segment_mm_gradw_workspace": (_i64, [_i64, _i64, _i32, _i32]),
+    "dgll_hip_segment_mm_gradw": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32,
+                                         _vp, _i64]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

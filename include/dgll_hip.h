@@ -1435,6 +1435,39 @@ int dgll_hip_radius(void* stream, const void* y, int64_t ld_y, int64_t m, const 
                     const int64_t* x_seg_ptr, int64_t n_segs, int dtype, int64_t D, float r2, int K, int exclude_self,
                     int64_t* out_rowptr, int32_t* out_col, float* out_dist, int64_t* out_nnz, int32_t* scratch);
 
+/* ---- Grouped dense products: y_i = x_i . W[type_i] (DGL's segment_mm / gather_mm; csrc/segment_mm.hip).
+ *   Segments  seglen int32 / int64 [R] ON THE DEVICE (seglen_bytes 4 / 8): rows [off_r, off_r + seglen[r]) of the row list belong to
+ *             segment r, off the exclusive prefix sum.  Nothing is read back: offsets are formed by the launch itself and CLAMPED to
+ *             [0, M] (a negative length counts as 0), so no seglen can make a kernel address outside its operands.
+ *   rows      int32 / int64 [M] or NULL (rows_bytes 4 / 8): position t of the row list is row rows[t] of a, c and g (NULL: row t).
+ *             An entry outside [0, M) is neither read nor written.
+ *   dtype     DGLL_F32 or DGLL_BF16: of a, c and g, and of the packed weights.  fp32 accumulation on the matrix cores
+ *             (v_mfma_f32_32x32x16_bf16 / v_mfma_f32_32x32x2_f32).  a and g: rows on 16-byte boundaries, pitch >= width rounded up to
+ *             16 bytes.  At most N = 256 output columns per call.
+ * dgll_hip_segment_mm_pack      all R weights W_r [K, N] -- element (r, k, n) at b + r stride_r + k stride_k + n stride_n, fp32 or bf16;
+ *                               the strides choose W_r or its transpose -- into the MFMA-fragment layout of dst_dtype the products
+ *                               read, dgll_hip_segment_mm_packed_bytes(R, K, N, dst_dtype) bytes, 16-byte aligned.
+ * dgll_hip_segment_mm           c[rows of segment r] = a[rows of segment r] . W_r; rows of the list no segment covers are ZEROS.
+ *                               Only segments [seg_begin, seg_end) are computed and `packed` holds those alone (a caller bounds
+ *                               the packed copy by running ranges of segments one after the other); the call with seg_begin == 0
+ *                               writes the zeros.  build_plan != 0 forms the tile list in `workspace` first; 0 reuses the list an
+ *                               earlier call with the same seglen, R and M left there (further ranges / column blocks).  workspace: dgll_hip_segment_mm_workspace(R) bytes (the tile list), 16-byte aligned.
+ * dgll_hip_segment_mm_gradw     gw[r] = a_r^T . g_r, fp32 [K, N] at gw + r gw_stride_r on pitch gw_ld, exactly zero for an empty
+ *                               segment; long segments are split over row slabs whose partials are summed in slab order.
+ *                               workspace: dgll_hip_segment_mm_gradw_workspace(M, R, K, N) bytes.
+ * No atomics: two runs give the same bits.  Nothing is allocated, synchronised or read back: the calls can be captured.            */
+int64_t dgll_hip_segment_mm_packed_bytes(int64_t R, int K, int N, int dtype);
+int dgll_hip_segment_mm_pack(void* stream, const void* b, int src_dtype, int64_t stride_r, int64_t stride_k, int64_t stride_n, int64_t R,
+                             int K, int N, int dst_dtype, void* packed);
+int64_t dgll_hip_segment_mm_workspace(int64_t R);
+int dgll_hip_segment_mm(void* stream, const void* a, int64_t lda, int dtype, const void* packed, const void* seglen, int seglen_bytes,
+                        int64_t R, const void* rows, int rows_bytes, void* c, int64_t ldc, int64_t M, int K, int N, int64_t seg_begin,
+                        int64_t seg_end, int build_plan, void* workspace, int64_t workspace_bytes);
+int64_t dgll_hip_segment_mm_gradw_workspace(int64_t M, int64_t R, int K, int N);
+int dgll_hip_segment_mm_gradw(void* stream, const void* a, int64_t lda, const void* g, int64_t ldg, int dtype, const void* seglen,
+                              int seglen_bytes, int64_t R, const void* rows, int rows_bytes, float* gw, int64_t gw_stride_r, int64_t gw_ld,
+                              int64_t M, int K, int N, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
