@@ -52,8 +52,41 @@ namespace dgll { extern std::string last_error; inline void set_error(const std:
 #define DGLL_REQUIRE(cond, msg) do { if (!(cond)) { ::dgll::set_error(std::string(msg) + " [" #cond "]"); return DGLL_ERR_INVALID; } } while (0)
 struct uint4 { uint32_t x, y, z, w; };
 inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
+struct uint2 { uint32_t x, y; };
+inline uint2 make_uint2(uint32_t a, uint32_t b) { return uint2{a, b}; }
+struct float4 { float x, y, z, w; };
+inline float4 make_float4(float a, float b, float c, float d) { return float4{a, b, c, d}; }
 inline float __uint_as_float(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+// The two matrix-core instructions of segment_mm.hip as wave-level collectives (as emu::shfl): every lane parks its operands, the wave
+// meets, every lane sums its 16 results in fp32, the wave meets again.  A lane that skips an MFMA its wave executes ends the run in
+// wave_barrier ("wave-level collective not reached by all lanes").  Layouts as the kernel's own comments give them: operand lane l holds
+// row (A) / column (B) l % 32 and the KPL consecutive k from KPL (l / 32); result register r of lane l is
+// D[(r & 3) + 8 (r >> 2) + 4 (l / 32)][l % 32].  The vector types are the kernel's own (templates: this file stays plain C++ for g++).
+namespace emu {
+inline unsigned char mfma_ops[256][32];        // per lane: 16 bytes of A, 16 bytes of B
+template <int KPL, class Elem, class A, class V16> inline V16 mfma(A a, A b, V16 c, float (*value)(Elem)) {
+    static_assert(sizeof(A) == KPL * sizeof(Elem) && sizeof(V16) == 64, "operand size");
+    memcpy(mfma_ops[cur], &a, sizeof(A)); memcpy(mfma_ops[cur] + 16, &b, sizeof(A));
+    wave_barrier();
+    float d[16]; memcpy(d, &c, 64);
+    const int base = cur & ~63, col = cur & 31, hi = (cur & 63) >> 5;
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        for (int h = 0; h < 2; ++h) {
+            Elem x[KPL], y[KPL];
+            memcpy(x, mfma_ops[base + 32 * h + row], sizeof(A)); memcpy(y, mfma_ops[base + 32 * h + col] + 16, sizeof(A));
+            for (int e = 0; e < KPL; ++e) d[r] += value(x[e]) * value(y[e]);
+        }
+    }
+    wave_barrier();
+    V16 out; memcpy(&out, d, 64); return out;
+}
+inline float f32_value(float v) { return v; }
+inline float bf16_value(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+}
+template <class V8, class V16> inline V16 __builtin_amdgcn_mfma_f32_32x32x16_bf16(V8 a, V8 b, V16 c, int, int, int) { return emu::mfma<8, uint16_t>(a, b, c, emu::bf16_value); }
+template <class V16> inline V16 __builtin_amdgcn_mfma_f32_32x32x2f32(float a, float b, V16 c, int, int, int) { return emu::mfma<1, float>(a, b, c, emu::f32_value); }
 namespace dgll {
 constexpr int kWave = 64, kBlock = 256, kWavesPerBlock = 4;
 typedef uint16_t bf16_t;
@@ -63,6 +96,11 @@ inline float bf16_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 inline uint32_t rne(float f) { uint32_t u = __float_as_uint(f); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; }
 inline uint32_t pack_bf16x2(float lo, float hi) { return rne(lo) | (rne(hi) << 16); }
 inline int64_t uniform64(int64_t v) { uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32)); return (int64_t)(((uint64_t)hi << 32) | lo); }
+inline float bf16_to_f32(bf16_t b) { return __uint_as_float((uint32_t)b << 16); }
+inline bf16_t f32_to_bf16(float f) { return (bf16_t)rne(f); }
+template <typename T> inline void store_one(T* p, float v);
+template <> inline void store_one<float>(float* p, float v) { *p = v; }
+template <> inline void store_one<bf16_t>(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 template <typename T, int EPV> struct VecIO;
 template <> struct VecIO<float, 4> {
     typedef uint4 raw_t;

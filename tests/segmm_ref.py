@@ -16,3 +16,26 @@ def grouped_refs(a, b, g, idx):
 
 def segment_ids(seglen):
     return torch.repeat_interleave(torch.arange(len(seglen)), torch.as_tensor(seglen))
+
+
+def gw_slab(m):
+    """Rows per slab of the weight gradient: max(512, M / 128) rounded up to 16 (the workspace comment of dgll_amd/ops_segmm.py)."""
+    return max(512, -(-(-(-m // 128)) // 16) * 16)
+
+
+def plan_ref(seglen, m, unit):
+    """(segoff, tileptr, partptr), R + 2 entries each, as the header comment of csrc/segment_mm.hip describes the tile list: lengths
+    clamped to [0, M], offsets their exclusive prefix sum clamped to [0, M], element R the pseudo segment of the rows behind the last
+    segment (segoff[R + 1] = M); tileptr the exclusive prefix of ceil(length / unit) with the total at R + 1; partptr the same prefix
+    over the tiles of the segments that have more than one."""
+    raw, segoff = 0, []
+    for v in list(seglen) + [m]:
+        segoff.append(min(raw, m))
+        raw += min(max(int(v), 0), m)
+    segoff.append(m)
+    tileptr, partptr = [0], [0]
+    for lo, hi in zip(segoff[:-1], segoff[1:]):
+        t = -(-(hi - lo) // unit)
+        tileptr.append(tileptr[-1] + t)
+        partptr.append(partptr[-1] + (t if t > 1 else 0))
+    return segoff, tileptr, partptr
