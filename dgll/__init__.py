@@ -36,6 +36,7 @@ _ALIASES = {
     "dgll.points": "dgll_amd.points",
     "dgll.nn.GlobalPooling": "dgll_amd.nn.GlobalPooling",
     "dgll.nn.GlobalPooling.Pooling": "dgll_amd.nn.GlobalPooling.Pooling",
+    "dgll.nn.GlobalPooling.select": "dgll_amd.nn.GlobalPooling.select",
     "dgll.data": "dgll_amd.data",
     "dgll.data.dgraph": "dgll_amd.data.dgraph",
     "dgll.sampling": "dgll_amd.sampling",

@@ -260,6 +260,9 @@ KNN_MAX_K, KNN_MAX_D = 64, 256              # DGLL_KNN_MAX_K, DGLL_KNN_MAX_D: th
 KNN_QUERY_TILE, KNN_CAND_TILE = 256, 32     # DGLL_KNN_QUERY_TILE, DGLL_KNN_CAND_TILE: its tile geometry
 FPS_MAX_D, FPS_MAX_REG_SEG = 32, 8192       # DGLL_FPS_MAX_D, DGLL_FPS_MAX_REG_SEG: dgll_hip_fps keeps dmin in registers up to that segment size
 RADIUS_MAX_K, RADIUS_MAX_D = 64, 32         # DGLL_RADIUS_MAX_K, DGLL_RADIUS_MAX_D: the limits of dgll_hip_radius
+SEGSORT_TILE = 4096                         # DGLL_SEGSORT_TILE: dgll_hip_segment_sort sorts a segment of up to this many rows in one workgroup
+POOL_MAX_F = 65536                          # DGLL_POOL_MAX_F: the widest row of dgll_hip_pool_select
+POOL_ACT_NONE, POOL_ACT_IDENTITY, POOL_ACT_TANH, POOL_ACT_SIGMOID = range(4)       # DGLL_POOL_ACT_*
 
 
 class DgllHipError(RuntimeError):
@@ -426,6 +429,9 @@ SIGNATURES = {
     "dgll_hip_segment_mm_gradw_workspace": (_i64, [_i64, _i64, _i32, _i32]),
     "dgll_hip_segment_mm_gradw": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i32, _i32,
                                          _vp, _i64]),
+    "dgll_hip_segment_sort": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "dgll_hip_pool_select": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64]),
+    "dgll_hip_pool_select_bwd": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -224,6 +224,7 @@ def _mm_f32(a, wt, relu, bias, addend, a2=None, wt2=None, gate=None):
     wt = wt.to(torch.float32)
     wt = wt if wt.stride(1) == 1 else wt.contiguous()
     m, k = a.shape
+    ldw = max(wt.stride(0), k) if wt.shape[0] == 1 else wt.stride(0)    # a one-row wt (a one-output layer's weight) has no pitch of its own
     n = wt.shape[0]
     k2 = 0
     if a2 is not None:
@@ -253,7 +254,7 @@ def _mm_f32(a, wt, relu, bias, addend, a2=None, wt2=None, gate=None):
         return None if t is None else t.data_ptr() + n0 * step
 
     for n0 in range(0, n, 256):
-        _lib.launch("dgll_hip_mm2_f32", a.device, a.data_ptr(), a.stride(0), at(wt, n0, 4 * wt.stride(0)), wt.stride(0), k,
+        _lib.launch("dgll_hip_mm2_f32", a.device, a.data_ptr(), a.stride(0), at(wt, n0, 4 * ldw), ldw, k,
                     _lib.ptr(a2), _lib.pitch(a2), at(wt2, n0, 4 * _lib.pitch(wt2)), _lib.pitch(wt2), k2,
                     at(out, n0), out.stride(0), m, min(256, n - n0), at(bias, n0), int(relu), at(addend, n0), _lib.pitch(addend),
                     at(gate, n0), _lib.pitch(gate))

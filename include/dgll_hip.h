@@ -1468,6 +1468,50 @@ int dgll_hip_segment_mm_gradw(void* stream, const void* a, int64_t lda, const vo
                               int seglen_bytes, int64_t R, const void* rows, int rows_bytes, float* gw, int64_t gw_stride_r, int64_t gw_ld,
                               int64_t M, int K, int N, void* workspace, int64_t workspace_bytes);
 
+/* ---- Ordering the rows of every segment by a score, and the scaled gather behind it (TopKPooling, SAGPooling, SortPooling;
+ * csrc/seg_sort.hip).
+ * dgll_hip_segment_sort
+ *   Inputs    score [n] of score_dtype (DGLL_F32 / DGLL_BF16; bf16 is converted exactly to fp32).  seg_ptr int64 [n_segs + 1] cuts the
+ *             rows into contiguous segments, empty ones allowed.  max_seg: no segment is larger (the host knows the sizes; it chooses
+ *             the kernel instance).
+ *   Order     inside a segment: SCORE DESCENDING, TIES TO THE SMALLER ROW INDEX.  -0.0 equals +0.0.  Every NaN ranks after -inf; NaNs
+ *             are ordered among themselves by index.  (One 64-bit key per row: a monotone image of the score above the offset inside
+ *             the segment.  Keys are unique, so the order is total and does not depend on the sorting network.)
+ *   Output    out_ptr int64 [n_segs + 1]: segment s yields the first m_s = out_ptr[s + 1] - out_ptr[s] rows of that order, cut to its
+ *             size, as global row ids in out_idx int64 [n_out] at out_ptr[s]; the slots of a segment behind its size (m_s > size_s: a
+ *             fixed number of slots per segment, SortPooling's padding) receive -1.  A slot outside [0, n_out) is not written.
+ *   out_inv   int32 [n] or NULL: a kept row holds its slot in out_idx, every other row -1.  All n entries are written by the launch,
+ *             the rows no segment covers included; nothing needs clearing beforehand.
+ *   scratch   16 n bytes, 16-byte aligned, needed (non-NULL) only when max_seg > DGLL_SEGSORT_TILE; its contents mean nothing.
+ *   Limits    n, n_segs, n_out < 2^31, max_seg <= 65535 DGLL_SEGSORT_TILE; anything else returns DGLL_ERR_INVALID and names the limit,
+ *             on the host before any launch.  n == 0, n_segs == 0 or n_out == 0 launch nothing.
+ *   Paths     max_seg <= 64: a wavefront per segment, keys in registers, cross-lane moves only (no LDS, no barrier).  max_seg <=
+ *             DGLL_SEGSORT_TILE: a workgroup per segment, keys in registers, LDS only for the strides that cross wavefronts.  Longer:
+ *             runs of DGLL_SEGSORT_TILE rows sorted into `scratch`, then ceil(log2(runs)) merge launches (correct, not tuned).
+ * dgll_hip_pool_select      out[j, :] = x[idx[j], :] * act(score[idx[j]]) for j < n_out; idx[j] outside [0, n) (the -1 of a padded
+ *             slot) gives a row of zeros, written by the same launch.  x [n, F] and out [n_out, F] of `dtype` on row pitches >= F;
+ *             16-byte accesses under the rule of dgll_hip_knn when x and out both allow them, scalar ones otherwise.  act is one of
+ *             DGLL_POOL_ACT_*; NONE ignores score (which may be NULL): a pure gather.  The multiplier is computed in fp32.
+ * dgll_hip_pool_select_bwd  one pass over the rows of x in order, inv as dgll_hip_segment_sort wrote it, g [n_out, F] the gradient of
+ *             out: a kept row i (j = inv[i] in [0, n_out)) gets grad_x[i, :] = g[j, :] * act(s_i) and grad_score[i] = act'(s_i) *
+ *             sum_c g[j, c] x[i, c] (fp32, reduced across the lanes of the row); every other row gets zeros in both.  grad_x [n, F] of
+ *             `dtype`, grad_score fp32 [n]; a NULL output skips that gradient.  No gather on x, no atomics, nothing cleared beforehand.
+ * No atomics and no grid-wide waits anywhere: two runs give the same bits.  Nothing is allocated, synchronised or read back: the calls
+ * can be captured into a graph.                                                                                                       */
+#define DGLL_SEGSORT_TILE 4096
+#define DGLL_POOL_MAX_F 65536
+#define DGLL_POOL_ACT_NONE 0
+#define DGLL_POOL_ACT_IDENTITY 1
+#define DGLL_POOL_ACT_TANH 2
+#define DGLL_POOL_ACT_SIGMOID 3
+int dgll_hip_segment_sort(void* stream, const void* score, int score_dtype, int64_t n, const int64_t* seg_ptr, int64_t n_segs,
+                          int64_t max_seg, const int64_t* out_ptr, int64_t* out_idx, int32_t* out_inv, int64_t n_out, void* scratch);
+int dgll_hip_pool_select(void* stream, const void* x, int64_t ld_x, int dtype, int64_t n, int64_t F, const void* score, int score_dtype,
+                         int act, const int64_t* idx, int64_t n_out, void* out, int64_t ld_out);
+int dgll_hip_pool_select_bwd(void* stream, const void* x, int64_t ld_x, int dtype, int64_t n, int64_t F, const void* score,
+                             int score_dtype, int act, const int32_t* inv, const void* g, int64_t ld_g, int64_t n_out, void* grad_x,
+                             int64_t ld_grad_x, float* grad_score);
+
 #ifdef __cplusplus
 }
 #endif
