@@ -263,6 +263,8 @@ RADIUS_MAX_K, RADIUS_MAX_D = 64, 32         # DGLL_RADIUS_MAX_K, DGLL_RADIUS_MAX
 SEGSORT_TILE = 4096                         # DGLL_SEGSORT_TILE: dgll_hip_segment_sort sorts a segment of up to this many rows in one workgroup
 POOL_MAX_F = 65536                          # DGLL_POOL_MAX_F: the widest row of dgll_hip_pool_select
 POOL_ACT_NONE, POOL_ACT_IDENTITY, POOL_ACT_TANH, POOL_ACT_SIGMOID = range(4)       # DGLL_POOL_ACT_*
+SPGEMM_WAVE_MAX, SPGEMM_LDS_MAX = 512, 4096 # DGLL_SPGEMM_WAVE_MAX, DGLL_SPGEMM_LDS_MAX: a row of C bounded by that many entries takes a wavefront / a workgroup
+SPGEMM_BWD_A, SPGEMM_BWD_B = 0, 1           # DGLL_SPGEMM_BWD_*
 
 
 class DgllHipError(RuntimeError):
@@ -432,6 +434,10 @@ SIGNATURES = {
     "dgll_hip_segment_sort": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "dgll_hip_pool_select": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64]),
     "dgll_hip_pool_select_bwd": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "dgll_hip_spgemm_scratch_bytes": (_sz, [_i64, _i64, _i64]),
+    "dgll_hip_spgemm_symbolic": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
+    "dgll_hip_spgemm_numeric": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]),
+    "dgll_hip_spgemm_bwd": (_i32, [_vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

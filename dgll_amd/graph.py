@@ -177,6 +177,14 @@ class CSRGraph:
             self._transpose = (gt, perm)
         return self._transpose
 
+    def __matmul__(self, other):
+        """self @ other for another CSRGraph: the sparse x sparse product ops_spgemm.spgemm(self, other)."""
+        if not isinstance(other, CSRGraph):
+            return NotImplemented
+        from .ops_spgemm import spgemm
+
+        return spgemm(self, other)
+
     def inv_degrees(self):
         """fp32[n_rows]: 1 / max(deg, 1) -- the mean reduce's row factor; cached."""
         if getattr(self, "_inv_deg", None) is None:

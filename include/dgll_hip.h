@@ -1512,6 +1512,49 @@ int dgll_hip_pool_select_bwd(void* stream, const void* x, int64_t ld_x, int dtyp
                              int score_dtype, int act, const int32_t* inv, const void* g, int64_t ld_g, int64_t n_out, void* grad_x,
                              int64_t ld_grad_x, float* grad_score);
 
+/* ---- Sparse x sparse products C = A . B, all three in CSR (csrc/spgemm.hip): coarsening S^T A S, metapaths, k-hop graphs.
+ *   Operands  A [M, K]: a_rowptr int64 [M + 1], a_col int32 [nnz_a], a_val fp32 [nnz_a] or NULL (all ones).  B [K, N] likewise.
+ *             PRECONDITION: the columns of every row of A and of B are strictly increasing.
+ *   Result    C [M, N]: c_rowptr int64 [M + 1], c_col int32 [nnz_c], c_val fp32 [nnz_c].  The columns of every row are strictly
+ *             increasing.  Entry (i, j) exists when some k lies in row i of A and in column j of B, whatever the values (a sum that
+ *             cancels to 0.0 stays).  Values are fp32 sums in a fixed order: no floating-point atomics, two runs give the same bits.
+ *   scratch   dgll_hip_spgemm_scratch_bytes(M, N, long_slots) bytes, 16-byte aligned, long_slots >= 1: a header, the class lists
+ *             (4 M bytes) and long_slots slots of about 4.25 N bytes (bitmap, word prefixes, dense sums) for the rows whose bound
+ *             exceeds DGLL_SPGEMM_LDS_MAX; more slots let more such rows run at once, one is enough for any input.  The SAME scratch
+ *             goes to the symbolic and then to the numeric call: the lists of the first are read by the second.
+ * dgll_hip_spgemm_symbolic  bounds every row by ub = min(products of the row, N), sorts the rows into three classes (ub <=
+ *             DGLL_SPGEMM_WAVE_MAX: a wavefront and an LDS table of that many keys per row; ub <= DGLL_SPGEMM_LDS_MAX: a workgroup and
+ *             an LDS table per row; above: a workgroup and a bitmap of N bits in the scratch), counts the distinct columns of every
+ *             row and writes c_rowptr [M + 1] and *total (device memory, int64) = nnz(C).  A row pointer or column id that is out
+ *             of range makes *total NEGATIVE (minus the error bits); c_rowptr means nothing then.  The caller reads *total back
+ *             (8 bytes: the one synchronisation of a product) to allocate c_col and c_val.
+ * dgll_hip_spgemm_numeric   fills c_col [nnz_c] and, unless c_val is NULL, c_val [nnz_c] for the c_rowptr the symbolic call wrote;
+ *             nnz_c is the total read back: a negative one returns DGLL_ERR_INVALID with the reason as text.
+ * dgll_hip_spgemm_bwd       gradient of the values of one operand, grad_x fp32 [nnz_x], from grad_c fp32 [nnz_c] on C's pattern
+ *             (M rows).  DGLL_SPGEMM_BWD_A: x = A (x_rows = M), y = B with its values: grad_x[(i, k)] = sum_j B[k, j] grad_c[i, j] over
+ *             row k of B.  DGLL_SPGEMM_BWD_B: x = B (x_rows = K), y = A^T [K, M] with A's values in A^T's order: grad_x[(k, j)] =
+ *             sum_i A[i, k] grad_c[i, j] over row k of A^T.  y_val NULL: all ones.  Eight lanes per entry of x, a binary search in
+ *             the sorted row of C per term, a fixed shuffle tree: no table, no atomics.
+ *   Limits    M, K, N, x_rows, y_rows and every nnz < 2^31; a NULL array, a limit exceeded or a scratch that is too small returns
+ *             DGLL_ERR_INVALID with a text, on the host before any launch.  M, K, N, nnz_a or nnz_b == 0 (and nnz_x == 0) launch
+ *             nothing and write nothing: the product is empty, c_rowptr all zeros, which the caller fills in.
+ * Apart from the caller's read-back nothing is allocated or synchronised.                                                            */
+#define DGLL_SPGEMM_WAVE_MAX 512
+#define DGLL_SPGEMM_LDS_MAX 4096
+#define DGLL_SPGEMM_BWD_A 0
+#define DGLL_SPGEMM_BWD_B 1
+size_t dgll_hip_spgemm_scratch_bytes(int64_t M, int64_t N, int64_t long_slots);
+int dgll_hip_spgemm_symbolic(void* stream, int64_t M, int64_t K, int64_t N, const int64_t* a_rowptr, const int32_t* a_col, int64_t nnz_a,
+                             const int64_t* b_rowptr, const int32_t* b_col, int64_t nnz_b, int64_t* c_rowptr, int64_t* total,
+                             void* scratch, int64_t scratch_bytes);
+int dgll_hip_spgemm_numeric(void* stream, int64_t M, int64_t K, int64_t N, const int64_t* a_rowptr, const int32_t* a_col,
+                            const float* a_val, int64_t nnz_a, const int64_t* b_rowptr, const int32_t* b_col, const float* b_val,
+                            int64_t nnz_b, const int64_t* c_rowptr, int32_t* c_col, float* c_val, int64_t nnz_c, void* scratch,
+                            int64_t scratch_bytes);
+int dgll_hip_spgemm_bwd(void* stream, int mode, int64_t x_rows, const int64_t* x_rowptr, const int32_t* x_col, int64_t nnz_x,
+                        int64_t y_rows, const int64_t* y_rowptr, const int32_t* y_col, const float* y_val, int64_t nnz_y, int64_t M,
+                        const int64_t* c_rowptr, const int32_t* c_col, const float* grad_c, int64_t nnz_c, float* grad_x);
+
 #ifdef __cplusplus
 }
 #endif
