@@ -10,6 +10,7 @@ from . import ops  # noqa: F401
 from . import backend  # noqa: F401
 from . import ops_segmm  # noqa: F401  (segment_mm / gather_mm: grouped products, a weight matrix per row type)
 from . import ops_spgemm  # noqa: F401  (spgemm: sparse x sparse CSR products; khop_graph, coarsen; CSRGraph @ CSRGraph)
+from . import ops_dense_attn  # noqa: F401  (segment_attention: dense attention inside every graph of a batch, on MFMA)
 from . import community  # noqa: F401  (CoG: size-capped Louvain communities, groups, CommunityBook)
 
 __version__ = "0.1.0"

@@ -267,6 +267,21 @@ SPGEMM_WAVE_MAX, SPGEMM_LDS_MAX = 512, 4096 # DGLL_SPGEMM_WAVE_MAX, DGLL_SPGEMM_
 SPGEMM_BWD_A, SPGEMM_BWD_B = 0, 1           # DGLL_SPGEMM_BWD_*
 
 
+class SegAttnDesc(C.Structure):
+    """include/dgll_hip.h: struct dgll_seg_attn_desc (dgll_hip_segment_attn_pass)."""
+    _fields_ = [("pass_", C.c_int), ("dtype", C.c_int),
+                ("seg_ptr", C.c_void_p), ("tile_ptr", C.c_void_p), ("n_rows", C.c_int64), ("n_segs", C.c_int64),
+                ("heads", C.c_int), ("D", C.c_int), ("scale", C.c_float),
+                ("q", C.c_void_p), ("ld_q", C.c_int64), ("k", C.c_void_p), ("ld_k", C.c_int64), ("v", C.c_void_p), ("ld_v", C.c_int64),
+                ("grad_out", C.c_void_p), ("ld_grad_out", C.c_int64), ("o", C.c_void_p), ("ld_o", C.c_int64),
+                ("out", C.c_void_p), ("ld_out", C.c_int64), ("out2", C.c_void_p), ("ld_out2", C.c_int64),
+                ("lse", C.c_void_p), ("delta", C.c_void_p)]
+
+
+SEG_ATTN_FORWARD, SEG_ATTN_ROWS, SEG_ATTN_COLS = 0, 1, 2
+SEG_ATTN_TILE, SEG_ATTN_MAX_D = 32, 128     # DGLL_SEG_ATTN_TILE, DGLL_SEG_ATTN_MAX_D: rows of a work item, the widest head
+
+
 class DgllHipError(RuntimeError):
     pass
 
@@ -438,6 +453,7 @@ SIGNATURES = {
     "dgll_hip_spgemm_symbolic": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64]),
     "dgll_hip_spgemm_numeric": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64]),
     "dgll_hip_spgemm_bwd": (_i32, [_vp, _i32, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "dgll_hip_segment_attn_pass": (_i32, [_vp, C.POINTER(SegAttnDesc)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

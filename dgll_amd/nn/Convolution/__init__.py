@@ -21,10 +21,12 @@ from .edgeconv import EdgeConv, DGCNN
 from ...knn import KNNGraph, SegmentedKNNGraph
 from .pointnetconv import PointNetConv, SetAbstraction, PointNet2
 from .typedlinear import TypedLinear
+from .gpsconv import GPSConv
 
 __all__ = ["gcnConv", "sageConv", "gatConv", "sparseGatConv", "GinConv", "GCN", "GIN",
            "GraphConvolution", "NeighborAggregator", "GraphSage", "SpecialSpmm", "SpecialSpmmFunction", "GAT", "SpGAT",
            "GATv2Conv", "GATv2", "DotGatConv", "TransformerConv", "GraphTransformer", "RelGraphConv", "RGCN", "AGNNConv", "AGNN",
            "PNAConv", "PNA", "GINEConv", "GINE", "CFConv", "ShiftedSoftplus", "GatedGCNConv", "GatedGCN",
            "ResGatedGraphConv", "ResGatedGCN", "GMMConv", "MoNet", "degree_pseudo", "GENConv", "DeeperGCN",
-           "EdgeConv", "DGCNN", "KNNGraph", "SegmentedKNNGraph", "PointNetConv", "SetAbstraction", "PointNet2", "TypedLinear"]
+           "EdgeConv", "DGCNN", "KNNGraph", "SegmentedKNNGraph", "PointNetConv", "SetAbstraction", "PointNet2", "TypedLinear",
+           "GPSConv"]

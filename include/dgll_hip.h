@@ -1555,6 +1555,43 @@ int dgll_hip_spgemm_bwd(void* stream, int mode, int64_t x_rows, const int64_t* x
                         int64_t y_rows, const int64_t* y_rowptr, const int32_t* y_col, const float* y_val, int64_t nnz_y, int64_t M,
                         const int64_t* c_rowptr, const int32_t* c_col, const float* grad_c, int64_t nnz_c, float* grad_x);
 
+/* ---- Dense attention inside every segment of a batch: three MFMA passes behind one entry point (csrc/seg_attn.hip) -----------------
+ * Per segment s (rows seg_ptr[s] .. seg_ptr[s + 1] of q, k, v, all [n_rows, heads * D]) and head of width D:
+ *     S = scale Q K^T     P = softmax over the keys of the segment     out = P V     lse[i] = log sum_j exp S_ij
+ * Rows never see another segment; an empty segment costs nothing; no [n, n] array exists in any pass.  `scale` is an argument and is
+ * never derived from D (the layers pad D).  With g = grad_out:
+ *   DGLL_SEG_ATTN_FORWARD  reads q, k, v; writes out [n_rows, heads * D] of `dtype` and lse fp32 [n_rows, heads].
+ *   DGLL_SEG_ATTN_ROWS     reads q, k, v, grad_out, o (the forward's out), lse; writes out = grad_q and delta fp32 [n_rows, heads],
+ *                          delta_i = <g_i, o_i>.
+ *   DGLL_SEG_ATTN_COLS     reads q, k, v, grad_out, lse, delta; writes out = grad_k and out2 = grad_v.
+ * seg_ptr int64 [n_segs + 1] (non-decreasing, seg_ptr[n_segs] = n_rows; clamped to [0, n_rows] on the device) and tile_ptr int64
+ * [n_segs + 1], tile_ptr[s] = sum over the segments before s of ceil(size / DGLL_SEG_ATTN_TILE): a work item is (segment, tile,
+ * head), one wavefront each, found by binary search in tile_ptr.  k and v may be the same buffer.
+ * Matrices of `dtype` (DGLL_F32 on v_mfma_f32_32x32x2_f32, DGLL_BF16 on v_mfma_f32_32x32x16_bf16; fp32 accumulation), unit column
+ * stride, pitches ld_* in elements: whole 16-byte vectors, 16-byte aligned bases, otherwise arbitrary (column slices of one
+ * projection).  D a multiple of the vector width (4 fp32 / 8 bf16 columns), at most DGLL_SEG_ATTN_MAX_D; n_rows, n_segs < 2^31.
+ * A NULL array or a limit exceeded returns DGLL_ERR_INVALID with a text, on the host before any launch; n_rows == 0 launches
+ * nothing.  No float atomics, no memset: two runs give the same bits.  No pass allocates, synchronises or reads anything back: the
+ * calls can be captured into a graph.                                                                                              */
+enum { DGLL_SEG_ATTN_FORWARD = 0, DGLL_SEG_ATTN_ROWS = 1, DGLL_SEG_ATTN_COLS = 2 };
+#define DGLL_SEG_ATTN_TILE 32
+#define DGLL_SEG_ATTN_MAX_D 128
+typedef struct dgll_seg_attn_desc {
+    int pass; int dtype;
+    const int64_t* seg_ptr; const int64_t* tile_ptr; int64_t n_rows; int64_t n_segs;
+    int heads; int D; float scale;
+    const void* q; int64_t ld_q;
+    const void* k; int64_t ld_k;
+    const void* v; int64_t ld_v;
+    const void* grad_out; int64_t ld_grad_out;
+    const void* o; int64_t ld_o;
+    void* out; int64_t ld_out;
+    void* out2; int64_t ld_out2;
+    float* lse;
+    float* delta;
+} dgll_seg_attn_desc;
+int dgll_hip_segment_attn_pass(void* stream, const dgll_seg_attn_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
